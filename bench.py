@@ -26,11 +26,21 @@ selects the other BASELINE configs (their lines are kept under profiles/, the dr
   cfg4  K = 64, 500 chunks, 100 particles            cfg5  K = 32, 500 chunks, 500 particles
   prod  the reference's production shape: 500 particles x a minibatch of 5 chunks x 100,000 sites
 
-Prints ONE JSON line on rank 0 (contract in the task statement), with two extra objects:
-"roofline" (dominant kernel = the backward kernel, timed with HIP events on its launch stream) and
-"cpu_baseline" (the oracle's C port on the host cores, bounded sample; a baseline, not the target);
-and, when oracle/_ref is built, "reference_kernel": the reference's own CUDA gradient kernel compiled
-unmodified for gfx950, timed on the same GPU on a bounded sample of the same rows.
+Prints ONE JSON line on rank 0 (metric, value, unit, higher_is_better, dtype, ms_per_step, ...), with
+"roofline" (dominant kernel = the backward kernel, timed with HIP events on its launch stream during the timed
+steps).  A plain run does only that: set-up, warm-up, the timed steps, the result checks and the line.
+
+--full adds what the headline figure does not need, all of it after the timed steps: "cpu_baseline" (the
+oracle's C port on the host cores, bounded sample; a baseline, not the target), "parity" (against the
+float64 oracle; the particle-space gradient f32 vs f64), the extra workloads of the default command
+("secondary" / "other_configs" at N = 1, "strong_cfg3" at N > 1), and, when oracle/_ref is built,
+"reference_kernel": the reference's own CUDA gradient kernel compiled unmodified for gfx950, timed on the
+same GPU on a bounded sample of the same rows.
+
+--dump-outputs DIR writes what the last timed step computed, as a caller of the step receives it, to
+DIR/<name>.npy (float64; rank 0): log_density [B] and grad_log_density [B, D] of the particles the step
+started from, and the SVGD state it returned: particles [B, D], svgd_mu / svgd_nu / svgd_nu_max [B, D],
+svgd_length_scale [1].  Inputs are seeded, so the same arguments give the same inputs on every run.
 """
 
 from __future__ import annotations
@@ -101,7 +111,12 @@ def parse():
     ap.add_argument("--autograd-step", action="store_true", help="chain rule by torch autograd instead of the fused HIP tail (dev A/B)")
     ap.add_argument("--variant", default="", help="R:T override for the kernel variant (dev)")
     ap.add_argument("--nrm", type=int, default=0, help="rescale interval override (dev; 0 = library default)")
+    ap.add_argument("--full", action="store_true", help="after the timed steps, also run the CPU baseline, the parity legs, "
+                    "the reference-kernel leg and the extra workloads (a plain run times the headline steps alone)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the last timed step's outputs to DIR/<name>.npy")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     cfg = CONFIGS[a.config]
     for key in ("K", "particles", "chunks", "chunk_size", "overlap"):
         if getattr(a, key) is None:
@@ -300,6 +315,27 @@ def self_launch(n: int) -> int:
     return min(worst, 255)
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(out_dir, logp, grad, state):
+    """--dump-outputs: the last timed step's outputs as float64 .npy files.  Should the particle rows pass 64 MB in all,
+    a fixed sample of them (seed 0) is written instead, their indices in sampled_rows.npy."""
+    arrays = {"log_density": logp, "grad_log_density": grad, "particles": state.particles,
+              "svgd_mu": state.mu, "svgd_nu": state.nu, "svgd_nu_max": state.nu_max}
+    arrays = {k: v.detach().double().cpu().numpy() for k, v in arrays.items()}
+    B = arrays["particles"].shape[0]
+    row_bytes = sum(v[0].nbytes for v in arrays.values())
+    if B * row_bytes > DUMP_BUDGET_BYTES:
+        rows = np.sort(np.random.default_rng(0).choice(B, DUMP_BUDGET_BYTES // (row_bytes + 8) - 1, replace=False))
+        arrays = {k: v[rows] for k, v in arrays.items()}
+        arrays["sampled_rows"] = rows.astype(np.float64)
+    arrays["svgd_length_scale"] = state.length_scale.detach().double().cpu().numpy().reshape(1)
+    os.makedirs(out_dir, exist_ok=True)
+    for k, v in arrays.items():
+        np.save(os.path.join(out_dir, f"{k}.npy"), v)
+
+
 def extra_workload(name, rank, world, dev, local_rank, use_dist, steps, warmup, het_rate=None, double=False, chunks=0):
     """A second workload timed in the same process AFTER the headline loop, with the same protocol (one discarded set-up
     step, ``warmup`` untimed steps, ``steps`` timed steps between barriers, max over ranks, HIP-event kernel times): the
@@ -495,6 +531,7 @@ def main():
     use_fused = not a.autograd_step and fused_step.fusable(template, kern)
 
     timing_only = os.environ.get("PHK_BENCH_TIMING_ONLY") == "1"
+    last = {}  # the latest step's (log density, gradient): device tensors, read only by --dump-outputs after the loop
 
     def one_step(state):
         nonlocal inds
@@ -504,7 +541,8 @@ def main():
         if use_fused:
             # what fit() runs: parameter map -> kernels -> chunk sums + flags -> (all-reduce) -> prior + chain rule,
             # a fixed sequence of HIP launches (phlash_amd/step.py), then the SVGD update
-            _, g = fused_step.log_density_and_grad(template, state.particles, (1.0, c1, 1.0), kern, inds, afs)
+            lp, g = fused_step.log_density_and_grad(template, state.particles, (1.0, c1, 1.0), kern, inds, afs)
+            last["logp"], last["grad"] = lp, g
             flags.add_(kern._flags)
             if timing_only:  # (timing-only library builds return garbage: the update is computed and dropped)
                 svgd.step(state, g, lr=0.1)
@@ -520,6 +558,7 @@ def main():
         if afs is not None:
             lp = lp + afs_term(mcp.to_dm(), afs)  # model.py:58-68 (torch float64 on the GPU; tiny next to the kernels)
         (g,) = torch.autograd.grad(lp.sum(), xs)
+        last["logp"], last["grad"] = lp.detach(), g
         return svgd.step(state, g, lr=0.1)
 
     def barrier():
@@ -614,11 +653,13 @@ def main():
                       f"no result line is printed", file=sys.stderr, flush=True)
             dist.destroy_process_group()
             sys.exit(4)
-    # extra workloads, same process, after the headline loop (all ranks take part; rank 0 keeps the dicts)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, last["logp"], last["grad"], state)
+    # --full: extra workloads, same process, after the headline loop (all ranks take part; rank 0 keeps the dicts)
     extras = {}
     sized_as_config = all(getattr(a, k) == CONFIGS[a.config][k] for k in ("K", "particles", "chunks", "chunk_size", "overlap"))
-    if (not a.no_extras and a.config == "cfg2" and sized_as_config and not a.double and not a.variant and a.het_rate is None
-            and a.pool_chunks == 0 and not a.autograd_step):
+    if (a.full and not a.no_extras and a.config == "cfg2" and sized_as_config and not a.double and not a.variant
+            and a.het_rate is None and a.pool_chunks == 0 and not a.autograd_step):
         if world == 1:
             # the reference's default problem (mcmc.py:119-121, 193): 500 particles x minibatch of 5 x 100,000 windows
             extras["secondary"] = extra_workload("prod", rank, world, dev, local_rank, use_dist, steps=50, warmup=5, het_rate=0.05)
@@ -780,7 +821,7 @@ def main():
             out["per_rank"] = per_rank
         if os.environ.get("PHK_LIB"):  # developer A/B builds: say so in the line
             out["PHK_LIB"] = os.environ["PHK_LIB"]
-        if not a.no_cpu_baseline and world == 1:  # the CPU leg (and the parity figure it yields) runs at N = 1 only
+        if a.full and not a.no_cpu_baseline and world == 1:  # the CPU leg (and the parity figure it yields) runs at N = 1 only
             # GPU ll of a bounded sample, then the oracle on the same sample (also the parity figure)
             with torch.no_grad():
                 mcp = template.from_flat(x0.to(dev))

@@ -129,11 +129,35 @@ def test_bench_plain_form_self_launches_two_ranks():
     assert 0 < line["config"]["het_rate"] < 0.2 and 0 < line["config"]["all_hom_word16_frac"] < 1
 
 
+def test_bench_plain_run_times_the_headline_alone_and_dumps_its_last_step(tmp_path):
+    """A plain ``python bench.py`` runs the headline steps alone (no CPU baseline, parity or extra workloads: those are
+    ``--full``), ``--steps`` timed steps, and ``--dump-outputs DIR`` writes the last timed step's outputs as float64 .npy;
+    with the same arguments the inputs are the same, so two runs agree within the north-star bar."""
+    args = ["--steps", "3", "--warmup", "1", "--particles", "12", "--chunks", "40", "--chunk-size", "4000"]
+    dumps = []
+    for run in ("a", "b"):
+        line = _plain_bench(args + ["--dump-outputs", str(tmp_path / run)])
+        assert line["steps"] == 3 and line["warmup"] == 1 and line["ms_per_step"] > 0
+        assert line["value"] == pytest.approx(12 * 40 * 4000 / (line["ms_per_step"] * 1e-3), rel=1e-6)
+        assert {"metric", "unit", "higher_is_better", "dtype"} <= set(line)
+        assert not {"cpu_baseline", "parity", "reference_kernel", "secondary", "other_configs"} & set(line), list(line)
+        d = {f[:-4]: np.load(tmp_path / run / f) for f in os.listdir(tmp_path / run)}
+        assert set(d) == {"log_density", "grad_log_density", "particles", "svgd_mu", "svgd_nu", "svgd_nu_max",
+                          "svgd_length_scale"}, sorted(d)
+        D = d["particles"].shape[1]
+        assert d["log_density"].shape == (12,) and d["svgd_length_scale"].shape == (1,)
+        assert all(d[k].shape == (12, D) for k in ("grad_log_density", "particles", "svgd_mu", "svgd_nu", "svgd_nu_max"))
+        assert all(v.dtype == np.float64 and np.isfinite(v).all() for v in d.values())
+        dumps.append(d)
+    np.testing.assert_allclose(dumps[0]["log_density"], dumps[1]["log_density"], rtol=1e-5)
+    np.testing.assert_allclose(dumps[0]["particles"], dumps[1]["particles"], rtol=1e-5, atol=1e-8)
+
+
 def test_bench_default_command_on_one_gpu_carries_the_other_shapes():
-    """``python bench.py`` at its default sizes: after the cfg2 loop the same process times the reference's production
+    """``python bench.py --full`` at its default sizes: after the cfg2 loop the same process times the reference's production
     shape (``secondary``) and BASELINE.json's cfg1, K = 64 and K = 32 configs (``other_configs``), each with the full inner
     step and its own checks; ``value`` stays the cfg2 figure."""
-    line = _plain_bench(["--steps", "2", "--warmup", "1", "--no-cpu-baseline", "--no-reference-kernel"], timeout=1500)
+    line = _plain_bench(["--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline", "--no-reference-kernel"], timeout=1500)
     assert line["n_gpus"] == 1 and line["config"]["name"] == "cfg2" and "strong_cfg3" not in line
     assert line["value"] == pytest.approx(100 * 500 * 60000 / (line["ms_per_step"] * 1e-3), rel=1e-6)
     sec = line["secondary"]
@@ -150,11 +174,11 @@ def test_bench_default_command_on_one_gpu_carries_the_other_shapes():
 
 
 def test_bench_default_command_at_two_ranks_carries_the_strong_scaling_extra():
-    """``python bench.py --gpus 2`` with the default (cfg2, weak scaling) sizes: after the headline loop the same launch
+    """``python bench.py --gpus 2 --full`` with the default (cfg2, weak scaling) sizes: after the headline loop the same launch
     times the cfg3 strong-scaling problem (a fixed total of chunk rows sharded over the ranks, AFS n = 20) and prints it
     as ``strong_cfg3``, leaving ``value`` the weak cfg2 figure.  Two ranks share the one GPU here (gloo), so the extra's
     5,000 rows are cut to 64 (--extras-chunks); the headline runs at full size."""
-    line = _plain_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--no-cpu-baseline",
+    line = _plain_bench(["--gpus", "2", "--steps", "2", "--warmup", "1", "--backend", "gloo", "--full", "--no-cpu-baseline",
                          "--extras-chunks", "64"], timeout=1500)
     assert line["n_gpus"] == 2 and line["scaling"] == "weak" and line["config"]["name"] == "cfg2"
     assert line["value"] == pytest.approx(2 * 100 * 500 * 60000 / (line["ms_per_step"] * 1e-3), rel=1e-6)
