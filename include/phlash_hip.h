@@ -112,6 +112,27 @@ int phk_loglik_prefolded(phk_handle* h, const void* params, int64_t pstride_b, i
                          const int64_t* inds, int64_t B, int64_t S, int64_t W, double* ll, void* grad, int grad_dlog,
                          void* stream);
 
+/* Posterior decoding, the quantity of Li & Durbin's `psmc -d` (the reference has no counterpart): the hidden-state
+ * posteriors gamma_t(k) = P(z_t = k | o) = alpha_t(k) beta_t(k) / sum_j alpha_t(j) beta_t(j) of every scored site
+ * t = W .. L-1 of each sequence (b, s), with alpha_0 = pi, alpha_t = (alpha_{t-1} A) .* e_{o_t}, beta_L = 1,
+ * beta_{t-1} = A (e_{o_t} .* beta_t), missing sites e = 1.  The posterior conditions on the whole row, warm-up included;
+ * there is no warm-up correction.  Sites are reduced over bins of `bin` >= 1 consecutive scored sites (the last bin may be
+ * partial; nbin = ceil((L - W) / bin)):
+ *   marginals  [B, S, nbin, K] in the handle's float type, or NULL: the mean of gamma_t over the bin's sites;
+ *   mean       [B, S, nbin] in the handle's float type, or NULL: the mean over the bin's sites of sum_k values_k gamma_t(k),
+ *              values device double [B, K] (row stride vstride_b; 0: one row [K] for every particle);
+ *   ll         [B, S] double, required: log P(o), the forward pass's by-product -- what phk_loglik without a gradient
+ *              returns (to the bit where both calls run the same forward variant, e.g. under phk_set_plan).
+ * At least one of marginals / mean.  params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as
+ * phk_loglik).  The call runs the forward leg (and, for a segmented plan, the beta-scan leg) of the plan a gradient call
+ * of this shape would use, then the decode sweep; a hybrid plan is run as its serial half.  Stream-ordered; no two calls
+ * on one handle may overlap.  The underflow flag (phk_underflow_risk) is raised as by phk_loglik: re-evaluate after
+ * phk_set_rescale_interval(h, 1).  PHK_EINVAL, before anything is enqueued, for a NULL handle, bin < 1, both outputs NULL,
+ * W outside [0, L], a NULL values with mean. */
+int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                  const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
+                  double* ll, void* mean, void* marginals, void* stream);
+
 /* Particle -> PSMCParams for a whole population in one launch, float64, with its Jacobian.
  * Replaces, for B particles at once: MCMCParams.to_dm (src/phlash/params.py:94-127),
  * SizeHistory.ect / .pi (src/phlash/size_history.py:123-138,170-193), transition_matrix + _expQ

@@ -26,6 +26,9 @@ def __getattr__(name):
     if name in ("PSMCParams", "MCMCParams"):
         from . import params
         return getattr(params, name)
+    if name == "posterior_tmrca":
+        from .decode import posterior_tmrca
+        return posterior_tmrca
     if name == "RawContig":
         from .data import RawContig
         return RawContig

@@ -18,6 +18,7 @@
 #define PHK_WITH_PACK 1
 #include "psmc_kernels.hip"
 #include "step_args.h"
+#include "decode_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -25,7 +26,8 @@ namespace phk {
     hipError_t launch_bwd_##tag(int R, int T, int nrm, const KArgs& a, int units, int nt, hipStream_t st);              \
     hipError_t launch_bscan_##tag(int R, int nrm, const KArgs& a, int64_t seg_sites, void* bseg, int32_t* fseg, int nt, \
                                   hipStream_t st);                                                                      \
-    hipError_t launch_finalize_##tag(const KArgs& a, int units, hipStream_t st);
+    hipError_t launch_finalize_##tag(const KArgs& a, int units, hipStream_t st);                                       \
+    hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -995,9 +997,10 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
     }
     *flag = (word & phk::FLAG_UNDERFLOW) ? 1 : 0;
     if (word & phk::FLAG_OVERRUN) {
-        static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel"};
+        static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel",
+                                            "decode_kernel (serial sweep)", "decode_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 4 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 6 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1445,6 +1448,156 @@ static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int
         }
     }
     return PHK_OK;
+}
+
+// Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
+// call of this shape would run, then the decode sweep instead of the gradient sweep.  The plan is read, never tuned or recorded:
+// decoding leaves the autotune cache and everything a gradient call decides unchanged.
+static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                          const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
+                          double* ll, void* mean, void* marginals, void* stream) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
+    if (!mean && !marginals) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
+    if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
+    if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
+    if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
+    if (B < 0 || S < 0 || vstride_b < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");
+    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    if (B == 0 || S == 0) return PHK_OK;
+    Launchers l;
+    if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    typedef hipError_t (*dec_fn)(int, int, const phk::KArgs&, const phk::DArgs&, int, int, hipStream_t);
+    dec_fn dec = nullptr;
+#define PHK_CASE(k) \
+    case k: dec = h->dbl ? phk::launch_decode_f64_##k : phk::launch_decode_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
+    const size_t rs = real_size(h);
+    const int K = h->K;
+    const int64_t nbin = (h->L - W + bin - 1) / bin;
+
+    // the checkpoint store is slabbed as for a gradient call
+    int64_t Bs = B, Ss = S;
+    {
+        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
+        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
+        if (B * S > max_seq) {
+            if (max_seq >= S) {
+                Bs = max_seq / S;
+            } else {
+                Bs = 1;
+                Ss = max_seq;
+            }
+        }
+        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
+    }
+    const int64_t nseq_launch = std::min(Bs, B) * std::min(Ss, S);
+    Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, 1), std::min(Bs, B));
+    const int Rf = plan.segmented ? plan.R1 : (plan.R1 ? plan.R1 : plan.R);  // the forward leg's variant
+    plan.hybrid_first = 0;  // a hybrid plan runs as its serial half
+    if (!valid_Rf(h, Rf) || !valid_T(K, Rf, plan.T)) return fail(PHK_EINVAL, "forward variant R=%d T=%d not available for K=%d", Rf, plan.T, K);
+    if (plan.segmented && !valid_Rf(h, plan.R2)) return fail(PHK_EINVAL, "beta-scan variant R=%d not available for K=%d", plan.R2, K);
+    const bool dense = dense_capable(h) && (Rf == 16 || (plan.segmented && plan.R2 == 16));
+    if (dense) {
+        const int64_t blocks = std::min(Bs, B) * (pstride_s != 0 ? std::min(Ss, S) : 1);
+        if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
+    }
+    const int units = plan.segmented ? (int)n_units(h, plan.T, W) : 0;
+
+    for (int64_t b0 = 0; b0 < B; b0 += Bs) {
+        const int64_t nb = std::min(Bs, B - b0);
+        for (int64_t s0 = 0; s0 < S; s0 += Ss) {
+            const int64_t ns = std::min(Ss, S - s0);
+            phk::KArgs a;
+            a.packed = h->packed;
+            a.Lw = h->Lw;
+            a.Ltot = h->L;
+            a.W = W;
+            a.inds = inds + s0;
+            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
+            a.pstride_b = pstride_b;
+            a.pstride_s = pstride_s;
+            a.B = nb;
+            a.S = ns;
+            a.ll = ll + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
+            a.ckpt = h->ckpt.p;
+            a.aux = (phk::SeqAux*)h->aux.p;
+            a.grad = nullptr;
+            a.gacc = (double*)h->gacc.p;
+            a.grad_dlog = 0;
+            a.eblk = (int16_t*)h->eblk.p;
+            a.eseg = (int32_t*)h->eseg.p;
+            a.seg_blocks = seg_blocks(plan.T);
+            a.bseg = h->bseg.p;
+            a.fseg = (const int32_t*)h->fseg.p;
+            a.bpi = (double*)h->bpi.p;
+            a.risk = (int*)h->risk.p;
+            a.seq_begin = a.seq_end = 0;
+            a.N = h->N;
+            a.part = nullptr;
+            a.ops_f = a.ops_b = nullptr;
+            a.asm_run = 0;
+            a.scan_prio = 0;
+            a.mask_runs = h->mask_runs;
+            a.pfstride_b = pstride_b / 7 * 5;
+            a.pfstride_s = pstride_s / 7 * 5;
+            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
+            {   // iteration budgets, twice what a healthy wave needs (see enqueue); a decode unit may walk up to one bin past its left edge
+                const int64_t nblk = (h->L + plan.T - 1) / plan.T, npieces = h->Lw / 4, G = a.seg_blocks;
+                const int64_t segW = W > 0 ? ((W - 1) / plan.T) / G : 0;
+                const int64_t need[4] = {npieces + 2 * (64 / plan.T) + 8, nblk + 8, npieces + 16, G * (segW + 1) + bin / plan.T + 8};
+                const int scale_of[4] = {0, 1, 2, 1};
+                for (int i = 0; i < 4; ++i)
+                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need[i] * h->budget_num[scale_of[i]] / h->budget_den[scale_of[i]], INT32_MAX);
+            }
+            if (dense) {
+                if (pstride_s == 0 && s0 > 0) {
+                    a.ops_f = (const float*)h->ops.p;
+                    a.ops_b = a.ops_f + nb * phk::DENSE_OPS_FLOATS;
+                } else if (int rc = build_dense_ops(h, &a, st); rc != PHK_OK) {
+                    return rc;
+                }
+            }
+            phk::DArgs d;
+            d.bin = bin;
+            d.nbin = nbin;
+            d.values = values ? values + b0 * vstride_b : nullptr;
+            d.vstride_b = vstride_b;
+            d.mean = mean ? (char*)mean + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
+            d.marg = marginals ? (char*)marginals + (size_t)((b0 * S + s0) * nbin * K) * rs : nullptr;
+            hipError_t e;
+            if (!plan.segmented) {
+                e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+                e = dec(plan.T, h->nrm, a, d, 0, 256, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "decode kernel launch (K=%d T=%d): %s", K, plan.T, hipGetErrorString(e));
+                continue;
+            }
+            // segmented: forward kernel || beta scan (second stream), then the decode units
+            HIP_TRY(hipEventRecord(h->ev_fork, st));
+            HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+            e = l.fwd(Rf, plan.T, h->nrm, true, a, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+            e = l.bscan(plan.R2, h->nrm, a, (int64_t)SEG_SITES, h->bseg.p, (int32_t*)h->fseg.p, 256, h->side);
+            if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
+            HIP_TRY(hipEventRecord(h->ev_join, h->side));
+            HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+            e = dec(plan.T, h->nrm, a, d, units, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "decode kernel launch (K=%d T=%d units=%d): %s", K, plan.T, units, hipGetErrorString(e));
+        }
+    }
+    return PHK_OK;
+}
+
+int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                  const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
+                  double* ll, void* mean, void* marginals, void* stream) {
+    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, values, vstride_b, ll, mean, marginals, stream);
 }
 
 }  // extern "C"

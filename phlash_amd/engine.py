@@ -226,3 +226,58 @@ class HipEngine:
         if grad and self.K_user != self.K:
             g = g[..., : self.K_user]
         return (ll, g) if grad else ll
+
+    def posterior(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, values: torch.Tensor | None = None,
+                  bin: int = 1, marginals: bool = True, mean: bool = False):
+        """Posterior decoding (``phk_posterior``, the quantity of ``psmc -d``): params / inds as ``run``.  Returns
+        (ll [B, S] float64, mean [B, S, nbin] or None, marginals [B, S, nbin, K] or None), the last two in the handle's float
+        type, over bins of ``bin`` scored sites (nbin = ceil((L - warmup) / bin)): the bin means of gamma_t and of
+        sum_k values_k gamma_t(k).  ``values`` [K] or [B, K] (float64 on the device) is required for ``mean``.  Padded
+        states (K below the compiled size) get value 0 and posterior 0; they are stripped from ``marginals``."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert marginals or mean, "nothing to decode: marginals and mean are both off"
+        assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+        vals, vstride = None, 0
+        if mean:
+            assert values is not None, "mean needs values"
+            vals = torch.as_tensor(values, dtype=torch.float64, device=self.device)
+            assert vals.shape[-1] == self.K_user and vals.ndim in (1, 2), vals.shape
+            if vals.ndim == 2:
+                assert vals.shape[0] == B
+            if pad_k:
+                vals = torch.cat([vals, vals.new_zeros(vals.shape[:-1] + (pad_k,))], -1)
+            vals = vals.contiguous()
+            vstride = self.K if vals.ndim == 2 else 0
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pf = None
+        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
+            p64 = params.contiguous()
+            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
+                                               None, ctypes.c_void_p(stream)))
+        else:
+            p = params.to(self.dtype).contiguous()
+        inds = inds.contiguous()
+        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        m = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device) if mean else None
+        g = torch.empty((B, S, nbin, self.K), dtype=self.dtype, device=self.device) if marginals else None
+        rc = _lib.load().phk_posterior(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            inds.data_ptr(), B, S, int(warmup), int(bin), vals.data_ptr() if vals is not None else None, vstride,
+            ll.data_ptr(), m.data_ptr() if m is not None else None, g.data_ptr() if g is not None else None, ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        if g is not None and pad_k:
+            g = g[..., : self.K_user]
+        return ll, m, g

@@ -16,6 +16,7 @@ What differs from the reference, by design:
 from __future__ import annotations
 
 import warnings
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -49,6 +50,24 @@ def _run_guarded(kern, *args, **kw):
         kern._eng.set_rescale_interval(1)
         out = kern._eng.run(*args, **kw)
     return out
+
+
+def _posterior_guarded(kern, *args, **kw):
+    """engine.posterior with the same safety net as ``_run_guarded`` (the decode sweep raises the same underflow flag)."""
+    out = kern._eng.posterior(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.posterior(*args, **kw)
+    return out
+
+
+class Posterior(NamedTuple):
+    """What ``PSMCKernel.posterior`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64
+    mean: torch.Tensor | None  # [..., nbin]: bin means of sum_k values_k gamma_t(k), or None without values
+    marginals: torch.Tensor | None  # [..., nbin, M]: bin means of gamma_t, or None
 
 
 class _LogLik(torch.autograd.Function):
@@ -207,6 +226,29 @@ class PSMCKernel:
         if want_numpy:
             dll = PSMCParams(*(a.cpu().numpy() for a in dll))
         return ll, dll
+
+    # ---- posterior decoding (psmc -d) ---------------------------------------------------------
+    def posterior(self, pp, index, *, values=None, bin: int = 1, marginals: bool = True) -> Posterior:
+        """Hidden-state posteriors gamma_t(k) = P(z_t = k | o) of the scored sites (the ``overlap`` warm-up sites are run,
+        conditioned on, and not reported) of chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes
+        as ``loglik``), as means over bins of ``bin`` sites: ``marginals`` [..., nbin, M] and, with ``values`` ([M] or
+        [B, M]: a value per state, e.g. ``dm.eta.ect()``), ``mean`` [..., nbin] = bin means of sum_k values_k gamma_t(k).
+        nbin = ceil((L - overlap) / bin).  Returns ``Posterior(ll, mean, marginals)``, device tensors in ``float_type``
+        (ll float64); no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            vals = None
+            if values is not None:
+                vals = _as_tensor(values, self.device)
+                if vals.ndim == 2 and vals.shape[0] == 1:
+                    vals = vals[0]
+            ll, m, g = _posterior_guarded(self, pa, inds, warmup=self.overlap, values=vals, bin=int(bin),
+                                          marginals=bool(marginals), mean=vals is not None)
+        strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
+        return Posterior(strip(ll), strip(m), strip(g))
 
     # ---- fused evaluation used by the sampler -------------------------------------------------
     def _inds_tensor(self, inds) -> torch.Tensor:
