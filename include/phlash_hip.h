@@ -133,6 +133,30 @@ int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t 
                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                   double* ll, void* mean, void* marginals, void* stream);
 
+/* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
+ * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
+ * precedes site 0, site t is step t + 1, a missing site has e = 1):
+ *   (z*_0, z*_1 .. z*_n) = argmax  pi(z_0) * prod_{t=1..n} A[z_{t-1}, z_t] * e_{o_{t-1}}(z_t)
+ *   logp = log of that maximum (natural log).
+ * Ties: among equal candidates the lowest predecessor index wins, and the lowest final state.  z*_0 is not reported.
+ *   logp         [B, S] double;
+ *   path         uint8 [B, S, path_stride], path_stride >= L - W: z*_{W+1} .. z*_n, the states at sites W .. n-1 (the
+ *                warm-up sites take part in the maximisation and are not reported; there is no warm-up correction of
+ *                logp); every byte past a row's own length is 255;
+ *   lens         device int64 [N], one own length per data row of the handle (W < lens[i] <= L), or NULL = L for all.
+ *                A short contig padded with missing windows is NOT the same problem: the best continuation through a
+ *                missing tail depends on the end state and can bend the last tract.  An entry out of range raises the
+ *                bad-index flag on the device (reported by phk_underflow_risk; the length is clamped).
+ * params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Two kernels per slab of the
+ * checkpoint store (phk_set_workspace_limit applies as to a gradient call): the max-product recursion with delta
+ * checkpointed every 16 sites (float64: 8), then the traceback.  No plan is tuned or recorded: the call leaves phk_get_plan and the
+ * bits of every later call unchanged.  Stream-ordered; no two calls on one handle may overlap.  The underflow flag is
+ * raised as by phk_loglik: re-evaluate after phk_set_rescale_interval(h, 1).  PHK_EINVAL, before anything is enqueued,
+ * for a NULL handle, NULL params / inds / logp / path, W outside [0, L), path_stride < L - W. */
+int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                const int64_t* inds, int64_t B, int64_t S, int64_t W, const int64_t* lens, double* logp, uint8_t* path,
+                int64_t path_stride, void* stream);
+
 /* Particle -> PSMCParams for a whole population in one launch, float64, with its Jacobian.
  * Replaces, for B particles at once: MCMCParams.to_dm (src/phlash/params.py:94-127),
  * SizeHistory.ect / .pi (src/phlash/size_history.py:123-138,170-193), transition_matrix + _expQ

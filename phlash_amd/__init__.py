@@ -29,6 +29,9 @@ def __getattr__(name):
     if name == "posterior_tmrca":
         from .decode import posterior_tmrca
         return posterior_tmrca
+    if name in ("viterbi_tmrca", "tmrca_segments"):
+        from . import decode
+        return getattr(decode, name)
     if name == "RawContig":
         from .data import RawContig
         return RawContig

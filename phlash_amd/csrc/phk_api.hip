@@ -19,6 +19,7 @@
 #include "psmc_kernels.hip"
 #include "step_args.h"
 #include "decode_args.h"
+#include "viterbi_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -27,7 +28,8 @@ namespace phk {
     hipError_t launch_bscan_##tag(int R, int nrm, const KArgs& a, int64_t seg_sites, void* bseg, int32_t* fseg, int nt, \
                                   hipStream_t st);                                                                      \
     hipError_t launch_finalize_##tag(const KArgs& a, int units, hipStream_t st);                                       \
-    hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -998,9 +1000,9 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
     *flag = (word & phk::FLAG_UNDERFLOW) ? 1 : 0;
     if (word & phk::FLAG_OVERRUN) {
         static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel",
-                                            "decode_kernel (serial sweep)", "decode_kernel (segment sweep)"};
+                                            "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 6 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 8 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1598,6 +1600,87 @@ int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t 
                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                   double* ll, void* mean, void* marginals, void* stream) {
     return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, values, vstride_b, ll, mean, marginals, stream);
+}
+
+// Viterbi decoding (phk_viterbi): the max-product forward kernel, then the traceback, per slab of the checkpoint store.  Like
+// posterior_impl it tunes and records nothing: the kernels have one layout per (real, K) and the handle's plan is not touched.
+int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
+                int64_t B, int64_t S, int64_t W, const int64_t* lens, double* logp, uint8_t* path, int64_t path_stride, void* stream) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    if (!params || !inds || !logp || !path) return fail(PHK_EINVAL, "params, inds, logp and path must be non-NULL device pointers");
+    if (W < 0 || W >= h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld)", (long long)W, (long long)h->L);
+    if (path_stride < h->L - W) return fail(PHK_EINVAL, "path_stride=%lld below L - W=%lld", (long long)path_stride, (long long)(h->L - W));
+    if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
+    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    if (B == 0 || S == 0) return PHK_OK;
+    typedef hipError_t (*vit_fn)(int, const phk::KArgs&, const phk::VArgs&, int, hipStream_t);
+    vit_fn vit = nullptr;
+#define PHK_CASE(k) \
+    case k: vit = h->dbl ? phk::launch_viterbi_f64_##k : phk::launch_viterbi_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    if (!vit) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
+    const size_t rs = real_size(h);
+    const int K = h->K;
+
+    // the checkpoint store is slabbed as for a gradient call (same bytes per sequence: delta every 8 sites in float64, every 16 in float32)
+    int64_t Bs = B, Ss = S;
+    {
+        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
+        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
+        if (B * S > max_seq) {
+            if (max_seq >= S) {
+                Bs = max_seq / S;
+            } else {
+                Bs = 1;
+                Ss = max_seq;
+            }
+        }
+        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
+    }
+    HIP_TRY(hipMemsetAsync(path, 0xff, (size_t)(B * S * path_stride), st));  // what no sequence writes: past its own length
+
+    for (int64_t b0 = 0; b0 < B; b0 += Bs) {
+        const int64_t nb = std::min(Bs, B - b0);
+        for (int64_t s0 = 0; s0 < S; s0 += Ss) {
+            const int64_t ns = std::min(Ss, S - s0);
+            phk::KArgs a;
+            std::memset(&a, 0, sizeof(a));
+            a.packed = h->packed;
+            a.Lw = h->Lw;
+            a.Ltot = h->L;
+            a.W = W;
+            a.inds = inds + s0;
+            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
+            a.pstride_b = pstride_b;
+            a.pstride_s = pstride_s;
+            a.B = nb;
+            a.S = ns;
+            a.ll = logp + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
+            a.ckpt = h->ckpt.p;
+            a.risk = (int*)h->risk.p;
+            a.N = h->N;
+            a.pfstride_b = pstride_b / 7 * 5;
+            a.pfstride_s = pstride_s / 7 * 5;
+            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
+            {   // iteration budgets, twice what a healthy wave needs: one iteration per block (8 or 16 sites) in either kernel
+                const int64_t need = (h->L + 7) / 8 + 8;
+                for (int i = 0; i < 2; ++i)
+                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need * h->budget_num[i] / h->budget_den[i], INT32_MAX);
+            }
+            phk::VArgs d;
+            d.lens = lens;
+            d.path = path + (b0 * S + s0) * path_stride;
+            d.path_stride = path_stride;
+            hipError_t e = vit(h->nrm, a, d, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "Viterbi kernel launch (K=%d): %s", K, hipGetErrorString(e));
+        }
+    }
+    return PHK_OK;
 }
 
 }  // extern "C"

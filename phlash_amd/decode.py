@@ -1,8 +1,9 @@
-"""Posterior decoding of whole contigs: the posterior mean TMRCA along the genome (what ``psmc -d`` reports), under one
-fitted model or averaged over the posterior sample ``fit`` returns.
+"""Decoding of whole contigs: the posterior mean TMRCA along the genome (what ``psmc -d`` reports), under one fitted model
+or averaged over the posterior sample ``fit`` returns, and the most probable TMRCA path (Viterbi) with its segments.
 
-The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.posterior`` -> ``phk_posterior``); this
-module only builds the models, pads ragged inputs and averages.  There is no CPU path.
+The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.posterior`` -> ``phk_posterior``), the paths
+from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``); this module only builds the models, pads ragged
+inputs, averages and run-length encodes.  There is no CPU path.
 """
 
 from __future__ import annotations
@@ -74,3 +75,69 @@ def posterior_tmrca(dms, data, window_size: int = 100, bin: int = 1, device=None
     if spans is None:
         return track
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
+def viterbi_tmrca(dm, data, window_size: int = 100, device=None, double_precision: bool = False):
+    """The most probable hidden path (Viterbi) of every row of ``data`` and its TMRCA track.
+
+    dm: one ``DemographicModel`` or a list of them (one path per model: most probable paths are not averaged), with theta
+        and rho per base pair, evaluated per window as in ``posterior_tmrca``.
+    data: int8 [N, L] het matrix of whole-contig rows, or a list of ``RawContig`` (or of int8 matrices) of different
+        lengths.  Ragged rows are decoded at their own lengths (a missing tail would bend the end of the path), not padded.
+    Returns ``(path, tmrca)``: the states (uint8) and ``dm.eta.ect()[path]`` (float64, the model's own time unit), on the
+    device.  For a matrix: [N, L] ([B, N, L] for a list of B models); for a list of contigs: a list with one such tensor
+    per contig, cut to the contig's length.
+    """
+    single = isinstance(dm, DemographicModel)
+    dms = [dm] if single else list(dm)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(m.M == M for m in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=m.eta, theta=float(m.theta) * window_size, rho=float(m.rho) * window_size) for m in dms]
+    pps = [PSMCParams.from_dm(m) for m in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    values = torch.stack([torch.as_tensor(m.eta.ect(), dtype=torch.float64) for m in dms]).to(dev)  # [B, M]
+    out = kern.viterbi(pp, torch.arange(rows.shape[0], device=dev), lens=lens)
+    path = out.path  # [B, N, L]
+    idx = path.long().clamp_(max=M - 1)  # (255 past a row's own length: cut away below)
+    track = torch.gather(values[:, None, :].expand(-1, path.shape[1], -1), 2, idx)
+    if single:
+        path, track = path[0], track[0]
+    if spans is None:
+        return path, track
+    return ([path[..., r : r + n, :length] for r, n, length in spans], [track[..., r : r + n, :length] for r, n, length in spans])
+
+
+def tmrca_segments(path, values=None):
+    """Run-length encoding of state paths on their device: ``path`` [L] or [N, L] (uint8 / integer tensor, 255 = past the
+    row's end) -> ``(row, start, end, state)`` int64 tensors, one entry per maximal run of one state in one row (sites
+    ``start .. end - 1``), rows in order; with ``values`` ([M], a value per state, e.g. ``dm.eta.ect()``) a fifth tensor
+    ``values[state]``.  Runs of 255 are dropped."""
+    p = torch.as_tensor(path)
+    if p.ndim == 1:
+        p = p[None]
+    assert p.ndim == 2, "path: [L] or [N, L]"
+    N, L = p.shape
+    # one key per site that changes wherever the state or the row does
+    key = p.reshape(-1).long() + 256 * torch.arange(N, device=p.device).repeat_interleave(L)
+    uniq, counts = torch.unique_consecutive(key, return_counts=True)
+    row, state = uniq // 256, uniq % 256
+    end = torch.cumsum(counts, 0) - row * L
+    start = end - counts
+    keep = state != 255
+    row, start, end, state = row[keep], start[keep], end[keep], state[keep]
+    if values is None:
+        return row, start, end, state
+    v = torch.as_tensor(values, dtype=torch.float64, device=p.device)
+    return row, start, end, state, v[state]

@@ -281,3 +281,45 @@ class HipEngine:
         if g is not None and pad_k:
             g = g[..., : self.K_user]
         return ll, m, g
+
+    def viterbi(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, lens: torch.Tensor | None = None):
+        """Viterbi decoding (``phk_viterbi``): params / inds as ``run``.  Returns (logp [B, S] float64, path [B, S, L - warmup]
+        uint8): the log probability of the single most probable hidden path of every sequence and its states at the sites
+        ``warmup .. L - 1``.  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
+        L``) cuts every row at its own length: bytes of ``path`` past it are 255.  Padded states (K below the compiled size)
+        are unreachable and never appear in a path."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert 0 <= int(warmup) < self.L
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+        if lens is not None:
+            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
+            lens = lens.contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pf = None
+        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
+            p64 = params.contiguous()
+            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
+                                               None, ctypes.c_void_p(stream)))
+        else:
+            p = params.to(self.dtype).contiguous()
+        inds = inds.contiguous()
+        n_out = self.L - int(warmup)
+        logp = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        path = torch.empty((B, S, n_out), dtype=torch.uint8, device=self.device)
+        rc = _lib.load().phk_viterbi(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            inds.data_ptr(), B, S, int(warmup), lens.data_ptr() if lens is not None else None, logp.data_ptr(), path.data_ptr(),
+            n_out, ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        return logp, path

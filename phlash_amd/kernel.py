@@ -62,6 +62,23 @@ def _posterior_guarded(kern, *args, **kw):
     return out
 
 
+def _viterbi_guarded(kern, *args, **kw):
+    """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
+    out = kern._eng.viterbi(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.viterbi(*args, **kw)
+    return out
+
+
+class Viterbi(NamedTuple):
+    """What ``PSMCKernel.viterbi`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    logp: torch.Tensor  # log probability of the most probable path (z_0 included), float64
+    path: torch.Tensor  # [..., L - overlap] uint8: its states at the scored sites; 255 past a row's own length
+
+
 class Posterior(NamedTuple):
     """What ``PSMCKernel.posterior`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
 
@@ -249,6 +266,27 @@ class PSMCKernel:
                                           marginals=bool(marginals), mean=vals is not None)
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Posterior(strip(ll), strip(m), strip(g))
+
+    # ---- Viterbi decoding ---------------------------------------------------------------------
+    def viterbi(self, pp, index, *, lens=None) -> Viterbi:
+        """The single most probable hidden path (max-product) of chunk(s) ``index`` under ``pp`` (PSMCParams or
+        DemographicModel, batch shapes as ``loglik``): ``Viterbi(logp, path)`` with ``path`` [..., L - overlap] uint8, the
+        states at the scored sites (the ``overlap`` warm-up sites take part in the maximisation and are not reported), and
+        ``logp`` the log probability of the whole path.  ``lens`` ([N] integers, one own length per row of the kernel's data,
+        ``overlap < len <= L``): rows end at their own length -- which is not the same as padding them with missing windows
+        -- and ``path`` holds 255 past it.  Ties go to the lowest state index.  No gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            logp, path = _viterbi_guarded(self, pa, inds, warmup=self.overlap, lens=lens)
+        return Viterbi(self._strip(logp, added_B, added_S), self._strip(path, added_B, added_S))
 
     # ---- fused evaluation used by the sampler -------------------------------------------------
     def _inds_tensor(self, inds) -> torch.Tensor:
