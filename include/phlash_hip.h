@@ -123,7 +123,8 @@ int phk_loglik_prefolded(phk_handle* h, const void* params, int64_t pstride_b, i
  *              values device double [B, K] (row stride vstride_b; 0: one row [K] for every particle);
  *   ll         [B, S] double, required: log P(o), the forward pass's by-product -- what phk_loglik without a gradient
  *              returns (to the bit where both calls run the same forward variant, e.g. under phk_set_plan).
- * At least one of marginals / mean.  params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as
+ * At least one of marginals / mean (with W = L there is no scored site: nbin = 0, ll = 0, both outputs are empty and may be
+ * NULL).  params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as
  * phk_loglik).  The call runs the forward leg (and, for a segmented plan, the beta-scan leg) of the plan a gradient call
  * of this shape would use, then the decode sweep; a hybrid plan is run as its serial half.  Stream-ordered; no two calls
  * on one handle may overlap.  The underflow flag (phk_underflow_risk) is raised as by phk_loglik: re-evaluate after

@@ -1460,8 +1460,9 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
                           double* ll, void* mean, void* marginals, void* stream) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
     if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
-    if (!mean && !marginals) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
+    // (W = L: no scored site, nbin = 0, ll = 0 -- the outputs are empty, and an empty device buffer may well be a null pointer)
+    if (!mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
     if (B < 0 || S < 0 || vstride_b < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");

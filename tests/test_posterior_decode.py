@@ -109,14 +109,16 @@ def _pp_np(pp, b):
                               float) for f in pn.PP._fields))
 
 
-def _oracle(pp, data, W, bin, values):
-    """-> marginals [B, S, nbin, K], mean [B, S, nbin], ll [B, S] for per-particle blocks broadcast over the rows"""
-    B = pp.d.shape[0]
+def _oracle(pp, data, W, bin, values, per_chunk=False):
+    """-> marginals [B, S, nbin, K], mean [B, S, nbin], ll [B, S] for per-particle blocks broadcast over the rows, fields
+    [B, K]; ``per_chunk``: for one block per (particle, chunk), fields [B * S, K]"""
+    S = len(data)
+    B = pp.d.shape[0] // (S if per_chunk else 1)
     M, MU, LL = [], [], []
     for b in range(B):
-        q = _pp_np(pp, b)
         ms, mus, lls = [], [], []
-        for row in data:
+        for s, row in enumerate(data):
+            q = _pp_np(pp, b * S + s if per_chunk else b)
             g, ll = po.forward_backward(q, row, W)
             ms.append(po.bin_means(g, bin))
             mus.append(po.bin_means(g @ values[b], bin))
@@ -142,19 +144,21 @@ def test_gamma_against_the_oracle(K, dbl):
 
     B, S, L = 2, 3, 700
     pp = _population(K, B, seed=K)
+    pc = _population(K, B * S, seed=1000 + K)  # the "chunk" layout: one model per (particle, chunk), all different
     values = np.stack([np.linspace(0.1, 5.0, K), np.arange(K, dtype=float)])
     worst = 0.0
     for rows, W in ((_rows(S, L, seed=1), 0), (_rows(S, L, seed=2, run=120), 37)):
         kern = get_kernel(K, rows, double_precision=dbl, overlap=W)
         for bin in (1, 7, 100):
-            M, MU, LL = _oracle(pp, rows[:, :], W, bin, values)
             for layout in ("bcast", "chunk"):
                 if layout == "bcast":
                     q = _bcast(pp)
-                else:  # one block per (particle, chunk): the same block repeated
+                    M, MU, LL = _oracle(pp, rows, W, bin, values)
+                else:  # one block per (particle, chunk), compared per chunk
                     from phlash_amd.params import PSMCParams
 
-                    q = PSMCParams(*(torch.as_tensor(a)[:, None].expand(B, S, K).contiguous() for a in pp))
+                    q = PSMCParams(*(torch.as_tensor(a).reshape(B, S, K).contiguous() for a in pc))
+                    M, MU, LL = _oracle(pc, rows, W, bin, values, per_chunk=True)
                 out = kern.posterior(q, np.arange(S), values=values, bin=bin)
                 m = out.marginals.double().cpu().numpy()
                 mu = out.mean.double().cpu().numpy()

@@ -18,6 +18,7 @@ import pytest
 import torch
 
 import viterbi_oracle as vo
+from decode_fuzz import structured_viterbi, sv32
 from oracle import psmc_numpy as pn
 
 # Exact path equality is only meaningful away from ties: every input row of the grid below has at least this distance (log
@@ -38,6 +39,8 @@ F32_LOGP_BAR = 1e-5
 
 GRID_K = [4, 8, 12, 16, 32, 64]
 GRID_SEEDS = {K: (K, 1, 2) for K in GRID_K}  # (population, rows A, rows B): chosen on the CPU so that MIN_MARGIN holds
+# population of the "chunk" layout, one model per (particle, chunk), all different: chosen on the CPU in the same way
+GRID_CHUNK_SEEDS = {4: 1004, 8: 1008, 12: 1012, 16: 1016, 32: 1032, 64: 1164}  # (the smallest margin of the grid stays 2e-5)
 GRID_L = 700
 GRID_LENS = (700, 523, 288)
 
@@ -81,30 +84,38 @@ def _bcast(pp):
     return PSMCParams(*(torch.as_tensor(a)[:, None] for a in pp))
 
 
-def _per_chunk(pp, S):
+def _per_chunk(pc, S):
+    """fields [B * S, K], one model per (particle, chunk) -> [B, S, K]"""
     from phlash_amd.params import PSMCParams
 
-    B, K = pp.d.shape
-    return PSMCParams(*(torch.as_tensor(a)[:, None].expand(B, S, K).contiguous() for a in pp))
+    return PSMCParams(*(torch.as_tensor(a).reshape(-1, S, a.shape[-1]).contiguous() for a in pc))
 
 
 def grid_inputs(K):
-    """The inputs of the oracle-parity tests for K states: a population of 2 models and two data sets,
+    """The inputs of the oracle-parity tests for K states: a population of 2 models ("bcast" layout: one block per particle),
+    a population of 2 x 3 models ("chunk" layout: one block per (particle, chunk), all different) and two data sets,
     (rows [3, 700], W, lens or None): isolated missing sites at W = 0, full rows; a run of 120 missing windows per row at
     W = 37, rows of their own lengths."""
     ps, sa, sb = GRID_SEEDS[K]
     pp = _population(K, 2, seed=ps)
-    return pp, [(_rows(3, GRID_L, seed=sa), 0, None), (_rows(3, GRID_L, seed=sb, run=120), 37, np.array(GRID_LENS))]
+    pc = _population(K, 2 * 3, seed=GRID_CHUNK_SEEDS[K])
+    return pp, pc, [(_rows(3, GRID_L, seed=sa), 0, None), (_rows(3, GRID_L, seed=sb, run=120), 37, np.array(GRID_LENS))]
 
 
-def oracle_grid(pp, rows, W, lens):
-    """-> paths [B][S] (uint8 [len - W]), logp [B, S], smallest margin"""
-    B = pp.d.shape[0]
+def grid_block(pp, pc, layout, b, s):
+    """the model of (particle b, chunk s) under a layout, as the oracle's PP"""
+    return _pp_np(pp, b) if layout == "bcast" else _pp_np(pc, b * 3 + s)
+
+
+def oracle_grid(pp, rows, W, lens, per_chunk=False):
+    """-> paths [B][S] (uint8 [len - W]), logp [B, S], smallest margin.  ``per_chunk``: pp holds one model per (particle,
+    chunk), [B * S, K]"""
+    B = pp.d.shape[0] // (len(rows) if per_chunk else 1)
     paths, logps, margin = [], np.empty((B, len(rows))), np.inf
     for b in range(B):
-        q = _pp_np(pp, b)
         ps = []
         for s, row in enumerate(rows):
+            q = _pp_np(pp, b * len(rows) + s if per_chunk else b)
             n = len(row) if lens is None else int(lens[s])
             p, lp, m = vo.viterbi(q, row[:n], W)
             ps.append(p)
@@ -145,70 +156,22 @@ def test_oracle_path_scores_its_own_logp():
     assert vo.viterbi(pp, data, 0)[1] <= pn.psmc_ll(pp, data)[1]  # max <= sum
 
 
-def structured_viterbi(pp, data):
-    """The step the kernels run, stated with loops in float64: the folded model (b, d, v) <- emis0 .* (b, d, v) with emission
-    rows (1, emis1 / emis0, 1 / emis0); per site delta'_j = e_j max(v_j max_{i<j} u_i delta_i, d_j delta_j, b_j max_{i>j}
-    delta_i) from one exclusive prefix maximum and one exclusive suffix maximum, each with the lowest index that reaches it;
-    linear domain, rescaled by the power of two of the maximum.  -> (path [n], logp)"""
-    e0, e1 = np.asarray(pp.emis0, float), np.asarray(pp.emis1, float)
-    b, d, v = (np.asarray(x, float) * e0 for x in (pp.b, pp.d, pp.v))
-    u = np.asarray(pp.u, float)
-    rows = [np.ones_like(e0), e1 / e0, 1.0 / e0]
-    K = len(e0)
-    delta = [float(x) for x in np.asarray(pp.pi, float)]
-    E = 0
-    back = []
-    for ob in data:
-        e = rows[2 if ob < 0 else min(int(ob), 1)]
-        pre, pa = [0.0] * K, [0] * K
-        run, arg = 0.0, 0
-        for j in range(K):
-            pre[j], pa[j] = run, arg
-            c = u[j] * delta[j]
-            if c > run:
-                run, arg = c, j
-        suf, sa = [0.0] * K, [K - 1] * K
-        run, arg = 0.0, K - 1
-        for j in range(K - 1, -1, -1):
-            suf[j], sa[j] = run, arg
-            if delta[j] >= run:
-                run, arg = delta[j], j
-        new, ptr = [0.0] * K, [0] * K
-        for j in range(K):
-            best, a = v[j] * pre[j], pa[j]
-            c = d[j] * delta[j]
-            if c > best:
-                best, a = c, j
-            c = b[j] * suf[j]
-            if c > best:
-                best, a = c, sa[j]
-            new[j], ptr[j] = best * e[j], a
-        ex = math.frexp(max(new))[1]
-        delta = [math.ldexp(x, -ex) for x in new]
-        E += ex
-        back.append(ptr)
-    z = max(range(K), key=lambda j: (delta[j], -j))
-    logp = E * math.log(2.0) + math.log(delta[z])
-    path = np.empty(len(data), dtype=np.uint8)
-    for t in range(len(data) - 1, -1, -1):
-        path[t] = z
-        z = back[t][z]
-    return path, logp
-
-
 @pytest.mark.parametrize("K", GRID_K)
 def test_structured_step_gives_the_oracle_path_on_the_gpu_inputs(K):
-    pp, sets = grid_inputs(K)
+    pp, pc, sets = grid_inputs(K)
     for rows, W, lens in sets:
-        paths, logps, margin = oracle_grid(pp, rows, W, lens)
-        assert margin >= MIN_MARGIN, f"K={K} W={W}: margin {margin:.2e} -- pick other seeds (GRID_SEEDS)"
-        for b in range(pp.d.shape[0]):
-            q = _pp_np(pp, b)
-            for s, row in enumerate(rows):
-                n = len(row) if lens is None else int(lens[s])
-                path, logp = structured_viterbi(q, row[:n])
-                assert np.array_equal(path[W:], paths[b][s]), (K, W, b, s)
-                assert abs(logp - logps[b, s]) < 1e-11 * abs(logps[b, s])
+        for layout in ("bcast", "chunk"):
+            paths, logps, margin = oracle_grid(pp, rows, W, lens) if layout == "bcast" else oracle_grid(pc, rows, W, lens, per_chunk=True)
+            assert margin >= MIN_MARGIN, f"K={K} W={W} {layout}: margin {margin:.2e} -- pick other seeds (GRID_SEEDS, GRID_CHUNK_SEEDS)"
+            for b in range(2):
+                for s, row in enumerate(rows):
+                    q = grid_block(pp, pc, layout, b, s)
+                    n = len(row) if lens is None else int(lens[s])
+                    path, logp = structured_viterbi(q, row[:n])
+                    assert np.array_equal(path[W:], paths[b][s]), (K, W, b, s, layout)
+                    assert abs(logp - logps[b, s]) < 1e-11 * abs(logps[b, s])
+                    if layout == "chunk" and s == b:  # ... and in float32 (what F32_VITERBI_DEFICIT_BAR records of this grid)
+                        assert np.array_equal(sv32(q, row[:n])[0][W:], paths[b][s]), (K, W, b, s, layout)
 
 
 def test_phk_viterbi_rejects_a_null_handle_without_a_device():
@@ -271,16 +234,17 @@ def _valid_path(pp_np, path):
 
 
 def _grid_calls(K, dbl):
-    """every call of the grid: yields (pp, b, s, row[:n], W, path_gpu [n - W], tail of the output row, logp_gpu)"""
+    """every call of the grid: yields (model of (b, s), b, s, row[:n], W, path_gpu [n - W], tail of the output row, logp_gpu,
+    layout)"""
     from phlash_amd.kernel import get_kernel
 
-    pp, sets = grid_inputs(K)
+    pp, pc, sets = grid_inputs(K)
     B = pp.d.shape[0]
     for rows, W, lens in sets:
         S, L = rows.shape
         kern = get_kernel(K, rows, double_precision=dbl, overlap=W)
         for layout in ("bcast", "chunk"):
-            q = _bcast(pp) if layout == "bcast" else _per_chunk(pp, S)
+            q = _bcast(pp) if layout == "bcast" else _per_chunk(pc, S)  # one block per (particle, chunk), all different
             with warnings.catch_warnings():
                 warnings.simplefilter("error")  # ordinary parameters: no underflow flag, no re-evaluation
                 out = kern.viterbi(q, np.arange(S), lens=lens)
@@ -289,21 +253,22 @@ def _grid_calls(K, dbl):
             for b in range(B):
                 for s in range(S):
                     n = L if lens is None else int(lens[s])
-                    yield pp, b, s, rows[s, :n], W, path[b, s, : n - W], path[b, s, n - W :], logp[b, s], layout
+                    yield grid_block(pp, pc, layout, b, s), b, s, rows[s, :n], W, path[b, s, : n - W], path[b, s, n - W :], logp[b, s], layout
 
 
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", GRID_K)
 def test_f64_path_equals_the_oracle_at_every_site(K):
-    pp, sets = grid_inputs(K)
+    pp, pc, sets = grid_inputs(K)
     ref = {}
     for rows, W, lens in sets:
-        paths, logps, margin = oracle_grid(pp, rows, W, lens)
-        assert margin >= MIN_MARGIN, f"K={K} W={W}: margin {margin:.2e}"
-        ref[W] = (paths, logps)
+        for layout in ("bcast", "chunk"):
+            paths, logps, margin = oracle_grid(pp, rows, W, lens) if layout == "bcast" else oracle_grid(pc, rows, W, lens, per_chunk=True)
+            assert margin >= MIN_MARGIN, f"K={K} W={W} {layout}: margin {margin:.2e}"
+            ref[W, layout] = (paths, logps)
     worst = 0.0
     for _, b, s, row, W, path, tail, logp, layout in _grid_calls(K, True):
-        paths, logps = ref[W]
+        paths, logps = ref[W, layout]
         assert (tail == 255).all(), (K, W, b, s, layout)
         diff = int((path != paths[b][s]).sum())
         assert diff == 0, f"K={K} W={W} b={b} s={s} {layout}: {diff} of {len(path)} sites differ from the oracle's path"
@@ -315,13 +280,15 @@ def test_f64_path_equals_the_oracle_at_every_site(K):
 @pytest.mark.gpu
 @pytest.mark.parametrize("K", GRID_K)
 def test_f32_path_is_almost_optimal(K):
-    pp, sets = grid_inputs(K)
-    ref = {W: oracle_grid(pp, rows, W, lens) for rows, W, lens in sets}
+    pp, pc, sets = grid_inputs(K)
+    ref = {}
+    for rows, W, lens in sets:
+        ref[W, "bcast"] = oracle_grid(pp, rows, W, lens)
+        ref[W, "chunk"] = oracle_grid(pc, rows, W, lens, per_chunk=True)
     worst_def, worst_lp, ndiff, nsite = 0.0, 0.0, 0, 0
-    for _, b, s, row, W, path, tail, logp, layout in _grid_calls(K, False):
-        paths, logps, _ = ref[W]
+    for q, b, s, row, W, path, tail, logp, layout in _grid_calls(K, False):
+        paths, logps, _ = ref[W, layout]
         assert (tail == 255).all() and int(path.max()) < K
-        q = _pp_np(pp, b)
         assert _valid_path(q, path)
         deficit = logps[b, s] - vo.path_logp(q, row, path, W)
         assert deficit >= -1e-9 * abs(logps[b, s]), "a path above the optimum: the oracle or the scoring is wrong"
