@@ -133,10 +133,11 @@
     auto uni_word = [&](const uint32_t rem) {
         if constexpr (DENSE) {
             float x = beta[0][0];
+            const int risk_exp = rem != 0u ? RISK_EXP_F32 : RISK_EXP_DEFERRED_F32;  // (as uni_block of fwd_kernel)
             auto resc = [&](float& y) -> int {
                 const int ex = lane.rescale1(y);
                 F += ex;
-                f_slack = min(f_slack, ex - RISK_EXP_DEFERRED_F32);
+                f_slack = min(f_slack, ex - risk_exp);
                 return 0;
             };
             if (__builtin_expect(rem == 0u, 1)) {  // all hom

@@ -199,10 +199,14 @@
         int dE = 0;
         if constexpr (DENSE) {
             float x = a[0][0];
+            // (a rescale inside a block that holds het / missing sites comes after at most four of them, like a group of four
+            // of the wave-vote path, and is held to the same threshold: 2^-80 out of four hets of emis1 / emis0 = 1e-6 passed
+            // the deferred one, and the sweep behind it returned NaN with the flag clear -- tests/test_model_fuzz.py, REGRESSIONS)
+            const int risk_exp = rem != 0u ? RISK_EXP_F32 : RISK_EXP_DEFERRED_F32;
             auto resc = [&](float& y) -> int {
                 const int ex = lane.rescale1(y);
                 dE += ex;
-                ex_slack = min(ex_slack, ex - RISK_EXP_DEFERRED_F32);
+                ex_slack = min(ex_slack, ex - risk_exp);
                 return 0;
             };
             if (T == 16 && __builtin_expect(rem == 0u, 1)) {

@@ -90,8 +90,7 @@ def _check(ll, g, ll_ref, g_ref, dbl, ll_atol=1e-5):
 # W = 0 draw 1.9e-4 of its row, smallest FULL that passes every draw 2.2e-4; float64 2.8e-13 and 1.1e-11.
 # Both precisions need the FULL term by a similar multiple of their epsilon: it is the conditioning of
 # a difference of two sweeps (see the test), not float32 slack.
-F32_GRAD_OWN, F32_GRAD_FULL = 1e-3, 5e-4
-F64_GRAD_OWN, F64_GRAD_FULL = 1e-9, 5e-11
+from parity_bars import F32_GRAD_FULL, F32_GRAD_OWN, F64_GRAD_FULL, F64_GRAD_OWN  # noqa: E402  (the values: tests/parity_bars.py)
 
 VARIANTS_16 = [(1, 8), (2, 8), (4, 8), (8, 8), (16, 8), (4, 16), (8, 16), (16, 16)]
 
