@@ -158,6 +158,37 @@ int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t ps
                 const int64_t* inds, int64_t B, int64_t S, int64_t W, const int64_t* lens, double* logp, uint8_t* path,
                 int64_t path_stride, void* stream);
 
+/* Posterior path sampling (forward-filtering backward-sampling; the reference has no counterpart): n_samples whole hidden
+ * paths z ~ P(z | o) of every sequence.  Conventions of phk_posterior: z_0 ~ pi precedes site 0, alpha_t is the forward
+ * vector after site t, a missing site has e = 1, the W warm-up sites condition the draw and are not reported.
+ * For sequence q = b * S + s -- (b, s) the position in THIS CALL, not in a slab and not the data row -- and sample r:
+ *   last site      the state at site L-1 is drawn with weights w_i = alpha_{L-1}(i);
+ *   earlier sites  for t = L-2 .. W the state at site t given state j at site t+1 is drawn with weights
+ *                    w_i = (u_i alpha_t(i)) v_j  (i < j),   d_j alpha_t(j)  (i = j),   b_j alpha_t(i)  (i > j):
+ *                  column j of the transition matrix times alpha_t (the kernels' folded factors of column j multiply every
+ *                  candidate alike);
+ *   one draw       c_i = inclusive prefix sum of w, theta = U c_{K-1}, state = #{ i <= K-2 : c_i <= theta } (the <= skips
+ *                  states of weight zero);
+ *   U              for (seed, q, r, site t): Philox4x32-10 with counter (t, r, q mod 2^32, q >> 32), key (seed mod 2^32,
+ *                  seed >> 32), multipliers 0xD2511F53 / 0xCD9E8D57, Weyl constants 0x9E3779B9 / 0xBB67AE85, output words
+ *                  x0 .. x3.  float64 kernels: U = (x0 2^21 + (x1 >> 11)) 2^-53; float32 kernels: U = (x0 >> 8) 2^-24,
+ *                  the top 24 bits of the same number.
+ * The generator is counter-based: sample r does not depend on n_samples, on the slabs (phk_set_workspace_limit) or on how
+ * the kernel groups samples, and the same seed gives the same bytes.  There is no lens: a draw over a row padded with
+ * missing windows has exactly the right marginal on the row's own sites (pad, then cut).
+ *   ll           [B, S] double: the forward kernel's by-product, bitwise what phk_posterior returns;
+ *   paths        uint8 [B, S, n_samples, path_stride], path_stride >= L - W: the states at sites W .. L-1.
+ * params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Per slab of the checkpoint
+ * store: the forward kernel of the plan a gradient call of this shape would run, as phk_posterior launches it, then the
+ * sampling traceback.  The plan is read, never tuned or recorded: the call leaves phk_get_plan and the bits of every later
+ * call unchanged.  Stream-ordered; no two calls on one handle may overlap.  The underflow flag is raised as by phk_loglik,
+ * and by a draw whose weights have no mass: re-evaluate after phk_set_rescale_interval(h, 1).  PHK_EINVAL, before anything
+ * is enqueued, for a NULL handle, NULL params / inds / ll / paths, W outside [0, L), n_samples outside [1, 65535],
+ * path_stride < L - W, and phk_viterbi's prefold rules. */
+int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, double* ll,
+                     uint8_t* paths, int64_t path_stride, void* stream);
+
 /* Particle -> PSMCParams for a whole population in one launch, float64, with its Jacobian.
  * Replaces, for B particles at once: MCMCParams.to_dm (src/phlash/params.py:94-127),
  * SizeHistory.ect / .pi (src/phlash/size_history.py:123-138,170-193), transition_matrix + _expQ

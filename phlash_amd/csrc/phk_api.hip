@@ -20,6 +20,7 @@
 #include "step_args.h"
 #include "decode_args.h"
 #include "viterbi_args.h"
+#include "sample_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -29,7 +30,8 @@ namespace phk {
                                   hipStream_t st);                                                                      \
     hipError_t launch_finalize_##tag(const KArgs& a, int units, hipStream_t st);                                       \
     hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st); \
-    hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);
+    hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);                   \
+    hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -1000,9 +1002,10 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
     *flag = (word & phk::FLAG_UNDERFLOW) ? 1 : 0;
     if (word & phk::FLAG_OVERRUN) {
         static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel",
-                                            "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel"};
+                                            "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel",
+                                            "sample_back_kernel"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 8 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 9 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1679,6 +1682,132 @@ int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t ps
             d.path_stride = path_stride;
             hipError_t e = vit(h->nrm, a, d, 256, st);
             if (e != hipSuccess) return fail(PHK_EHIP, "Viterbi kernel launch (K=%d): %s", K, hipGetErrorString(e));
+        }
+    }
+    return PHK_OK;
+}
+
+// Posterior path sampling (phk_sample_paths): the forward leg of the plan a gradient call of this shape would run, launched as
+// posterior_impl launches it (same variant, same operators, no beta scan: ll is phk_posterior's to the bit), then the sampling
+// traceback.  Like posterior_impl it reads the plan and tunes and records nothing.
+int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
+                     int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, double* ll, uint8_t* paths, int64_t path_stride,
+                     void* stream) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    if (!params || !inds || !ll || !paths) return fail(PHK_EINVAL, "params, inds, ll and paths must be non-NULL device pointers");
+    if (W < 0 || W >= h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld)", (long long)W, (long long)h->L);
+    if (n_samples < 1 || n_samples > 65535) return fail(PHK_EINVAL, "n_samples=%lld outside [1, 65535]", (long long)n_samples);
+    if (path_stride < h->L - W) return fail(PHK_EINVAL, "path_stride=%lld below L - W=%lld", (long long)path_stride, (long long)(h->L - W));
+    if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
+    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    if (B == 0 || S == 0) return PHK_OK;
+    Launchers l;
+    if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    typedef hipError_t (*smp_fn)(int, int, const phk::KArgs&, const phk::SArgs&, int, hipStream_t);
+    smp_fn smp = nullptr;
+#define PHK_CASE(k) \
+    case k: smp = h->dbl ? phk::launch_sample_f64_##k : phk::launch_sample_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    if (!smp) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
+    const size_t rs = real_size(h);
+    const int K = h->K;
+
+    // the checkpoint store is slabbed as for a gradient call
+    int64_t Bs = B, Ss = S;
+    {
+        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
+        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
+        if (B * S > max_seq) {
+            if (max_seq >= S) {
+                Bs = max_seq / S;
+            } else {
+                Bs = 1;
+                Ss = max_seq;
+            }
+        }
+        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
+    }
+    const int64_t nseq_launch = std::min(Bs, B) * std::min(Ss, S);
+    Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, 1), std::min(Bs, B));
+    const int Rf = plan.segmented ? plan.R1 : (plan.R1 ? plan.R1 : plan.R);  // the forward leg's variant
+    if (!valid_Rf(h, Rf) || !valid_T(K, Rf, plan.T)) return fail(PHK_EINVAL, "forward variant R=%d T=%d not available for K=%d", Rf, plan.T, K);
+    const bool dense = dense_capable(h) && Rf == 16;
+    if (dense) {
+        const int64_t blocks = std::min(Bs, B) * (pstride_s != 0 ? std::min(Ss, S) : 1);
+        if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
+    }
+
+    for (int64_t b0 = 0; b0 < B; b0 += Bs) {
+        const int64_t nb = std::min(Bs, B - b0);
+        for (int64_t s0 = 0; s0 < S; s0 += Ss) {
+            const int64_t ns = std::min(Ss, S - s0);
+            phk::KArgs a;
+            a.packed = h->packed;
+            a.Lw = h->Lw;
+            a.Ltot = h->L;
+            a.W = W;
+            a.inds = inds + s0;
+            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
+            a.pstride_b = pstride_b;
+            a.pstride_s = pstride_s;
+            a.B = nb;
+            a.S = ns;
+            a.ll = ll + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
+            a.ckpt = h->ckpt.p;
+            a.aux = (phk::SeqAux*)h->aux.p;
+            a.grad = nullptr;
+            a.gacc = (double*)h->gacc.p;
+            a.grad_dlog = 0;
+            a.eblk = (int16_t*)h->eblk.p;
+            a.eseg = (int32_t*)h->eseg.p;
+            a.seg_blocks = seg_blocks(plan.T);
+            a.bseg = h->bseg.p;
+            a.fseg = (const int32_t*)h->fseg.p;
+            a.bpi = (double*)h->bpi.p;
+            a.risk = (int*)h->risk.p;
+            a.seq_begin = a.seq_end = 0;
+            a.N = h->N;
+            a.part = nullptr;
+            a.ops_f = a.ops_b = nullptr;
+            a.asm_run = 0;
+            a.scan_prio = 0;
+            a.mask_runs = h->mask_runs;
+            a.pfstride_b = pstride_b / 7 * 5;
+            a.pfstride_s = pstride_s / 7 * 5;
+            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
+            {   // iteration budgets, twice what a healthy wave needs (see enqueue); the traceback makes one iteration per block
+                const int64_t nblk = (h->L + plan.T - 1) / plan.T, npieces = h->Lw / 4;
+                const int64_t need[4] = {npieces + 2 * (64 / plan.T) + 8, nblk + 8, npieces + 16, nblk + 8};
+                const int scale_of[4] = {0, 1, 2, 1};
+                for (int i = 0; i < 4; ++i)
+                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need[i] * h->budget_num[scale_of[i]] / h->budget_den[scale_of[i]], INT32_MAX);
+            }
+            if (dense) {
+                if (pstride_s == 0 && s0 > 0) {
+                    a.ops_f = (const float*)h->ops.p;
+                    a.ops_b = a.ops_f + nb * phk::DENSE_OPS_FLOATS;
+                } else if (int rc = build_dense_ops(h, &a, st); rc != PHK_OK) {
+                    return rc;
+                }
+            }
+            phk::SArgs d;
+            d.paths = paths;
+            d.path_stride = path_stride;
+            d.n_samples = n_samples;
+            d.seed = seed;
+            d.b0 = b0;
+            d.s0 = s0;
+            d.S_call = S;
+            // (the forward kernel of a segmented plan runs with the workgroup it has beside the beta scan, as in posterior_impl)
+            hipError_t e = l.fwd(Rf, plan.T, h->nrm, true, a, plan.segmented ? 256 : FWD_NT, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+            e = smp(plan.T, h->nrm, a, d, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "sampling kernel launch (K=%d T=%d): %s", K, plan.T, hipGetErrorString(e));
         }
     }
     return PHK_OK;

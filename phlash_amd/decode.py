@@ -1,8 +1,10 @@
 """Decoding of whole contigs: the posterior mean TMRCA along the genome (what ``psmc -d`` reports), under one fitted model
-or averaged over the posterior sample ``fit`` returns, and the most probable TMRCA path (Viterbi) with its segments.
+or averaged over the posterior sample ``fit`` returns, the most probable TMRCA path (Viterbi) with its segments, and TMRCA
+paths drawn from the posterior.
 
 The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.posterior`` -> ``phk_posterior``), the paths
-from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``); this module only builds the models, pads ragged
+from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sampling traceback (``PSMCKernel.sample_paths`` ->
+``phk_sample_paths``); this module only builds the models, pads ragged
 inputs, averages and run-length encodes.  There is no CPU path.
 """
 
@@ -117,6 +119,46 @@ def viterbi_tmrca(dm, data, window_size: int = 100, device=None, double_precisio
     if spans is None:
         return path, track
     return ([path[..., r : r + n, :length] for r, n, length in spans], [track[..., r : r + n, :length] for r, n, length in spans])
+
+
+def sample_tmrca(dms, data, n_samples: int = 1, seed: int = 0, window_size: int = 100, device=None, double_precision: bool = False):
+    """Hidden paths drawn from the posterior, z ~ P(z | o), of every row of ``data``, and their TMRCA tracks.
+
+    dms: one ``DemographicModel`` or a list of B of them (e.g. what ``fit()`` returns: ``n_samples`` paths per model are then
+        draws from the joint posterior over size history and path), with theta and rho per base pair, evaluated per window as
+        in ``posterior_tmrca``.
+    data: int8 [N, L] het matrix of whole-contig rows, or a list of ``RawContig`` (or of int8 matrices) of different
+        lengths: they are padded with missing windows and the padding is cut away again (unlike a most probable path, a
+        draw over the padded row has exactly the right distribution on the row's own sites).
+    Returns ``(paths, tmrca)``: the states (uint8) and ``dm.eta.ect()[paths]`` (float64, the model's own time unit), on the
+    device.  For a matrix: [N, n_samples, L] ([B, N, n_samples, L] for a list of B models); for a list of contigs: a list with
+    one such tensor per contig, cut to the contig's length.  The same ``seed`` gives the same paths.
+    """
+    single = isinstance(dms, DemographicModel)
+    dms = [dms] if single else list(dms)
+    assert len(dms) > 0, "no model to sample under"
+    M = dms[0].M
+    assert all(m.M == M for m in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=m.eta, theta=float(m.theta) * window_size, rho=float(m.rho) * window_size) for m in dms]
+    pps = [PSMCParams.from_dm(m) for m in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    values = torch.stack([torch.as_tensor(m.eta.ect(), dtype=torch.float64) for m in dms]).to(dev)  # [B, M]
+    out = kern.sample_paths(pp, torch.arange(rows.shape[0], device=dev), n_samples=n_samples, seed=seed)
+    paths = out.paths  # [B, N, n_samples, L]
+    track = torch.gather(values[:, None, None, :].expand(-1, paths.shape[1], paths.shape[2], -1), 3, paths.long())
+    if single:
+        paths, track = paths[0], track[0]
+    if spans is None:
+        return paths, track
+    return ([paths[..., r : r + n, :, :length] for r, n, length in spans], [track[..., r : r + n, :, :length] for r, n, length in spans])
 
 
 def tmrca_segments(path, values=None):

@@ -323,3 +323,42 @@ class HipEngine:
         )
         _lib.check(rc)
         return logp, path
+
+    def sample_paths(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, n_samples: int = 1, seed: int = 0):
+        """Posterior path sampling (``phk_sample_paths``): params / inds as ``run``.  Returns (ll [B, S] float64, paths
+        [B, S, n_samples, L - warmup] uint8): ``n_samples`` draws z ~ P(z | o) of every sequence at the sites ``warmup .. L - 1``
+        (the warm-up sites condition the draws).  Draw r of sequence (b, s) of the call is a function of ``seed``, b * S + s, r
+        and the site alone (a counter-based generator).  Padded states (K below the compiled size) have no mass and are never
+        drawn."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert 0 <= int(warmup) < self.L and 1 <= int(n_samples) <= 65535 and 0 <= int(seed) < 1 << 64
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pf = None
+        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
+            p64 = params.contiguous()
+            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
+                                               None, ctypes.c_void_p(stream)))
+        else:
+            p = params.to(self.dtype).contiguous()
+        inds = inds.contiguous()
+        n_out = self.L - int(warmup)
+        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        paths = torch.empty((B, S, int(n_samples), n_out), dtype=torch.uint8, device=self.device)
+        rc = _lib.load().phk_sample_paths(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            inds.data_ptr(), B, S, int(warmup), int(n_samples), int(seed), ll.data_ptr(), paths.data_ptr(), n_out,
+            ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        return ll, paths

@@ -72,6 +72,24 @@ def _viterbi_guarded(kern, *args, **kw):
     return out
 
 
+def _sample_guarded(kern, *args, **kw):
+    """engine.sample_paths with the same safety net as ``_run_guarded`` (the forward kernel raises the same underflow flag, and so
+    does a draw whose weights have no mass)."""
+    out = kern._eng.sample_paths(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.sample_paths(*args, **kw)
+    return out
+
+
+class PathSample(NamedTuple):
+    """What ``PSMCKernel.sample_paths`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    paths: torch.Tensor  # [..., n_samples, L - overlap] uint8: the sampled states at the scored sites
+
+
 class Viterbi(NamedTuple):
     """What ``PSMCKernel.viterbi`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
 
@@ -287,6 +305,21 @@ class PSMCKernel:
                 assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
             logp, path = _viterbi_guarded(self, pa, inds, warmup=self.overlap, lens=lens)
         return Viterbi(self._strip(logp, added_B, added_S), self._strip(path, added_B, added_S))
+
+    # ---- posterior path sampling ---------------------------------------------------------------
+    def sample_paths(self, pp, index, *, n_samples: int = 1, seed: int = 0) -> PathSample:
+        """``n_samples`` whole hidden paths drawn from the posterior, z ~ P(z | o), of chunk(s) ``index`` under ``pp`` (PSMCParams
+        or DemographicModel, batch shapes as ``loglik``): ``PathSample(ll, paths)`` with ``paths`` [..., n_samples, L - overlap]
+        uint8, the states at the scored sites (the ``overlap`` warm-up sites condition the draws and are not reported).
+        Forward filtering, backward sampling; the uniforms come from a counter-based generator keyed by ``seed``: draw r of a
+        sequence depends on (seed, the sequence's position in the call, r, site) only, not on ``n_samples``.  No gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            ll, paths = _sample_guarded(self, pa, inds, warmup=self.overlap, n_samples=int(n_samples), seed=int(seed))
+        return PathSample(self._strip(ll, added_B, added_S), self._strip(paths, added_B, added_S))
 
     # ---- fused evaluation used by the sampler -------------------------------------------------
     def _inds_tensor(self, inds) -> torch.Tensor:
