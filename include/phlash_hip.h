@@ -134,6 +134,42 @@ int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t 
                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                   double* ll, void* mean, void* marginals, void* stream);
 
+/* Transition posteriors (the reference has no counterpart): the pair posterior xi_t(i, j) = P(z_prev = i, z_t = j | o) of every
+ * scored site t = W .. L-1 of each sequence (b, s), split by how state k at the site was reached.  Conventions of
+ * phk_posterior: z_0 ~ pi precedes site 0 (it is z_prev of site 0), site t is step t + 1, alpha_t is the forward vector after
+ * site t with alpha_{-1} = pi, beta_L = 1, a missing site has e = 1, the W warm-up sites are conditioned on and not reported,
+ * and there is no warm-up correction.  With A[i,j] = b_j (i > j), d_j (i = j), u_i v_j (i < j), w = e_{o_t} .* beta_t and Z_t
+ * the sum of all three terms over k:
+ *   stay_t(k) = P(z_prev = k, z_t = k | o) = alpha_{t-1}(k) d_k w(k) / Z_t
+ *   up_t(k)   = P(z_prev < k, z_t = k | o) = (sum_{i<k} u_i alpha_{t-1}(i)) v_k w(k) / Z_t      (a move to an older state)
+ *   down_t(k) = P(z_prev > k, z_t = k | o) = (sum_{i>k} alpha_{t-1}(i)) b_k w(k) / Z_t          (a move to a younger state)
+ * so stay + up + down = gamma_t(k), the marginal phk_posterior reports.  d_k contains "recombined and coalesced again in the
+ * same interval": up and down count changes of the TMRCA STATE, not recombination events.  Sites are reduced over bins of
+ * `bin` >= 1 consecutive scored sites (the last bin may be partial; nbin = ceil((L - W) / bin)):
+ *   arrivals   [B, S, nbin, 3, K] in the handle's float type, or NULL: the MEAN over the bin's sites of (stay, up, down), in
+ *              that order;
+ *   changes    [B, S, nbin, 2] in the handle's float type, or NULL: the SUM over the bin's sites of (sum_k up_t(k),
+ *              sum_k down_t(k)) -- the expected number of moves to an older and to a younger state inside the bin; their
+ *              total is the expected number of TMRCA changes.  The sum over states is taken in float64;
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N], one own length per data row of the handle (W < lens[i] <= L), or NULL = L for all.  A site
+ *              at or past its row's own length adds nothing to a sum and is not counted in a mean; a bin without a site of
+ *              the row's own is written as zeros.  The row is still conditioned on as a whole: pad with missing windows,
+ *              whose beta is 1 -- the padded sites themselves carry the prior's change rate, which is what the mask keeps out.
+ *              An entry out of range raises the bad-index flag on the device (reported by phk_underflow_risk; the length is
+ *              clamped).
+ * At least one of arrivals / changes (with W = L there is no scored site: nbin = 0, ll = 0, both outputs are empty and may be
+ * NULL).  params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs, slabs
+ * (phk_set_workspace_limit) and stream ordering are phk_posterior's: the forward leg (and, for a segmented plan, the beta-scan
+ * leg) of the plan a gradient call of this shape would use, then the transition sweep; a hybrid plan is run as its serial half;
+ * the plan is read, never tuned or recorded.  Every bin is written once, by one unit: the same bits for any slab and any order
+ * of the units.  Stream-ordered; no two calls on one handle may overlap.  The underflow flag is raised as by phk_loglik:
+ * re-evaluate after phk_set_rescale_interval(h, 1).  PHK_EINVAL, before anything is enqueued, for a NULL handle, NULL params /
+ * inds / ll, bin < 1, both outputs NULL, W outside [0, L]. */
+int phk_transitions(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll,
+                    void* arrivals, void* changes, void* stream);
+
 /* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
  * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
  * precedes site 0, site t is step t + 1, a missing site has e = 1):

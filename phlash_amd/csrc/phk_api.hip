@@ -21,6 +21,7 @@
 #include "decode_args.h"
 #include "viterbi_args.h"
 #include "sample_args.h"
+#include "trans_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -31,7 +32,8 @@ namespace phk {
     hipError_t launch_finalize_##tag(const KArgs& a, int units, hipStream_t st);                                       \
     hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);                   \
-    hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);
+    hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);                \
+    hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -1003,9 +1005,9 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
     if (word & phk::FLAG_OVERRUN) {
         static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel",
                                             "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel",
-                                            "sample_back_kernel"};
+                                            "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 9 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 11 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1455,17 +1457,27 @@ static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int
     return PHK_OK;
 }
 
+// what phk_transitions hands to posterior_impl in place of mean / marginals
+struct TransOut {
+    const int64_t* lens;
+    void* arrivals;
+    void* changes;
+};
+
 // Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
 // call of this shape would run, then the decode sweep instead of the gradient sweep.  The plan is read, never tuned or recorded:
 // decoding leaves the autotune cache and everything a gradient call decides unchanged.
+// tr != nullptr (phk_transitions): the same legs, slabs and stream ordering with the transition sweep (launch_trans.hip) in the
+// decode sweep's place; values, mean and marginals are unused then.
 static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                           const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
-                          double* ll, void* mean, void* marginals, void* stream) {
+                          double* ll, void* mean, void* marginals, void* stream, const TransOut* tr = nullptr) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
     if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
     if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
     // (W = L: no scored site, nbin = 0, ll = 0 -- the outputs are empty, and an empty device buffer may well be a null pointer)
-    if (!mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
+    if (tr && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
+    if (!tr && !mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
     if (B < 0 || S < 0 || vstride_b < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");
@@ -1478,6 +1490,12 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     dec_fn dec = nullptr;
 #define PHK_CASE(k) \
     case k: dec = h->dbl ? phk::launch_decode_f64_##k : phk::launch_decode_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    typedef hipError_t (*trn_fn)(int, int, const phk::KArgs&, const phk::TArgs&, int, int, hipStream_t);
+    trn_fn trn = nullptr;
+#define PHK_CASE(k) \
+    case k: trn = h->dbl ? phk::launch_trans_f64_##k : phk::launch_trans_f32_##k; break;
     switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
 #undef PHK_CASE
     HIP_TRY(hipSetDevice(h->device));
@@ -1576,12 +1594,18 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             d.vstride_b = vstride_b;
             d.mean = mean ? (char*)mean + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
             d.marg = marginals ? (char*)marginals + (size_t)((b0 * S + s0) * nbin * K) * rs : nullptr;
+            phk::TArgs t;
+            t.bin = bin;
+            t.nbin = nbin;
+            t.lens = tr ? tr->lens : nullptr;
+            t.arr = tr && tr->arrivals ? (char*)tr->arrivals + (size_t)((b0 * S + s0) * nbin * 3 * K) * rs : nullptr;
+            t.chg = tr && tr->changes ? (char*)tr->changes + (size_t)((b0 * S + s0) * nbin * 2) * rs : nullptr;
             hipError_t e;
             if (!plan.segmented) {
                 e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-                e = dec(plan.T, h->nrm, a, d, 0, 256, st);
-                if (e != hipSuccess) return fail(PHK_EHIP, "decode kernel launch (K=%d T=%d): %s", K, plan.T, hipGetErrorString(e));
+                e = tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", tr ? "transition" : "decode", K, plan.T, hipGetErrorString(e));
                 continue;
             }
             // segmented: forward kernel || beta scan (second stream), then the decode units
@@ -1593,8 +1617,9 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
             HIP_TRY(hipEventRecord(h->ev_join, h->side));
             HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            e = dec(plan.T, h->nrm, a, d, units, 256, st);
-            if (e != hipSuccess) return fail(PHK_EHIP, "decode kernel launch (K=%d T=%d units=%d): %s", K, plan.T, units, hipGetErrorString(e));
+            e = tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
+            if (e != hipSuccess)
+                return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", tr ? "transition" : "decode", K, plan.T, units, hipGetErrorString(e));
         }
     }
     return PHK_OK;
@@ -1604,6 +1629,13 @@ int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t 
                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                   double* ll, void* mean, void* marginals, void* stream) {
     return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, values, vstride_b, ll, mean, marginals, stream);
+}
+
+int phk_transitions(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* arrivals,
+                    void* changes, void* stream) {
+    const TransOut tr = {lens, arrivals, changes};
+    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
 }
 
 // Viterbi decoding (phk_viterbi): the max-product forward kernel, then the traceback, per slab of the checkpoint store.  Like

@@ -79,6 +79,47 @@ def posterior_tmrca(dms, data, window_size: int = 100, bin: int = 1, device=None
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
 
 
+def posterior_changes(dms, data, window_size: int = 100, bin: int = 1, device=None, double_precision: bool = False):
+    """Expected number of TMRCA changes per bin of ``bin`` windows, for every row of ``data``: the breakpoint track.
+
+    For each bin, (moves to an older state, moves to a younger state): the sums over the bin's windows of
+    P(z_prev < z_t | o) and P(z_prev > z_t | o), exact (``PSMCKernel.transitions``), not estimated from sampled paths.  A
+    change is a change of the TMRCA state; a recombination that coalesces again in the same interval is not one.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``; the tracks
+        are averaged with equal weight.
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, and the padded windows count nothing (each
+        row's own length goes to the kernel, which masks them: a padded window would otherwise add the prior's change rate).
+    Returns float64 [N, ceil(L / bin), 2] on the device for a matrix, a list of such tensors (one per contig) for a list.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.transitions(pp, torch.arange(rows.shape[0], device=dev), bin=bin, lens=lens, arrivals=False)
+    track = out.changes.to(torch.float64).mean(0)  # [N, nbin, 2]: equal weight per model
+    if spans is None:
+        return track
+    return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
 def viterbi_tmrca(dm, data, window_size: int = 100, device=None, double_precision: bool = False):
     """The most probable hidden path (Viterbi) of every row of ``data`` and its TMRCA track.
 

@@ -62,6 +62,16 @@ def _posterior_guarded(kern, *args, **kw):
     return out
 
 
+def _transitions_guarded(kern, *args, **kw):
+    """engine.transitions with the same safety net as ``_run_guarded`` (the transition sweep raises the same underflow flag)."""
+    out = kern._eng.transitions(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.transitions(*args, **kw)
+    return out
+
+
 def _viterbi_guarded(kern, *args, **kw):
     """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
     out = kern._eng.viterbi(*args, **kw)
@@ -88,6 +98,14 @@ class PathSample(NamedTuple):
 
     ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
     paths: torch.Tensor  # [..., n_samples, L - overlap] uint8: the sampled states at the scored sites
+
+
+class Transitions(NamedTuple):
+    """What ``PSMCKernel.transitions`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    changes: torch.Tensor  # [..., nbin, 2]: bin sums of the expected moves to an older / a younger state
+    arrivals: torch.Tensor | None  # [..., nbin, 3, M]: bin means of (stay, up, down) per state, or None
 
 
 class Viterbi(NamedTuple):
@@ -284,6 +302,32 @@ class PSMCKernel:
                                           marginals=bool(marginals), mean=vals is not None)
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Posterior(strip(ll), strip(m), strip(g))
+
+    # ---- transition posteriors ------------------------------------------------------------------
+    def transitions(self, pp, index, *, bin: int = 1, lens=None, arrivals: bool = True) -> Transitions:
+        """Pair posteriors of adjacent sites, split by how the state at a scored site was reached: ``arrivals``
+        [..., nbin, 3, M], the bin means of stay_t(k) = P(z_prev = k, z_t = k | o), up_t(k) = P(z_prev < k, z_t = k | o) and
+        down_t(k) = P(z_prev > k, z_t = k | o) (they add up to the marginal ``posterior`` reports), and ``changes``
+        [..., nbin, 2], the bin SUMS of sum_k up_t(k) and sum_k down_t(k): the expected number of moves to an older and to a
+        younger TMRCA state inside the bin (a change of state, not a recombination event: a recombination that coalesces
+        again in the same interval stays).  Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as
+        ``loglik``); bins of ``bin`` scored sites, nbin = ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length
+        per row of the kernel's data, ``overlap < len <= L``): sites at or past a row's own length add nothing and are not
+        counted in a mean.  Returns ``Transitions(ll, changes, arrivals)``, device tensors in ``float_type`` (ll float64);
+        no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            ll, c, a = _transitions_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens, arrivals=bool(arrivals))
+        strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
+        return Transitions(strip(ll), strip(c), strip(a))
 
     # ---- Viterbi decoding ---------------------------------------------------------------------
     def viterbi(self, pp, index, *, lens=None) -> Viterbi:

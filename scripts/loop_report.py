@@ -4,6 +4,11 @@ closes (VALU / SALU / LDS / global / scratch / branches).  A hot loop that touch
 
     python scripts/loop_report.py <object or .so> <substring of the mangled kernel name> [min instructions]
 
+The block loops of the decoding sweeps (K = 16 float32, T = 16, NRM = 4, segmented; the outermost-but-two loop is the block loop):
+
+    python scripts/loop_report.py phlash_amd/csrc/build/launch_decode_f32_16.o decode_kernelIfLi16ELi4ELi16ELi4ELb1 3000
+    python scripts/loop_report.py phlash_amd/csrc/build/launch_trans_f32_16.o trans_kernelIfLi16ELi4ELi16ELi4ELb1 5000
+
 tests/test_layout.py imports ``kernel_loops`` to hold the sweeps' block loops to "no scratch access".
 """
 import os
