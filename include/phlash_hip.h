@@ -170,6 +170,37 @@ int phk_transitions(phk_handle* h, const void* params, int64_t pstride_b, int64_
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll,
                     void* arrivals, void* changes, void* stream);
 
+/* Leave-one-out predictive decoding (the reference has no counterpart): for every scored site t = W .. L-1 of each sequence
+ * (b, s), the probability that the site is het given every OTHER site of the row, P(o_t = het | o_{-t}, o_t observed), and the
+ * log of that predictive at the observation the site has.  Conventions of phk_posterior and phk_transitions: z_0 ~ pi precedes
+ * site 0, alpha_{t-1} is the forward vector before site t with alpha_{-1} = pi, beta_L = 1 and beta_t includes the emissions of
+ * sites t+1 .. L-1 only, a missing site has e = 1, the W warm-up sites are conditioned on and not reported, and there is no
+ * warm-up correction.  With A[i,j] = b_j (i > j), d_j (i = j), u_i v_j (i < j):
+ *   c_t(k)  = (alpha_{t-1} A)(k) beta_t(k)               the cavity weight: everything but site t's own emission
+ *   n0_t    = sum_k c_t(k) emis0(k)       n1_t = sum_k c_t(k) emis1(k)
+ *   phet_t  = n1_t / (n0_t + n1_t)
+ *   score_t = log(n_{o_t} / (n0_t + n1_t)) at an observed site (o_t = 0 or >= 1), 0 at a missing site.
+ * The emission rows need not sum to one (they are clamped upstream): the division by n0 + n1 keeps the definition exact.  Sites
+ * are reduced over bins of `bin` >= 1 consecutive scored sites (the last bin may be partial; nbin = ceil((L - W) / bin)):
+ *   track      [B, S, nbin, 3] in the handle's float type: the SUM over the bin's sites, accumulated in float64 and rounded once,
+ *              of [0] phet_t over the OBSERVED sites (the expected het count where there is an observed count to hold it
+ *              against), [1] phet_t over the MISSING sites (the imputed het count under the mask), [2] score_t (the
+ *              leave-one-out log score; missing sites add 0);
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N] or NULL, exactly as phk_transitions: a site at or past its row's own length adds nothing, a bin
+ *              without a site of the row's own is written as zeros, an entry outside (W, L] is clamped and raises the bad-index
+ *              flag.
+ * A site whose n0 + n1 is not positive adds nothing and raises the underflow flag (re-evaluate after
+ * phk_set_rescale_interval(h, 1)).  With W = L there is no scored site: nbin = 0, ll = 0, track is empty and may be NULL.
+ * params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs, slabs
+ * (phk_set_workspace_limit) and stream ordering are phk_posterior's, with the predictive sweep in the decode sweep's place; the
+ * plan is read, never tuned or recorded.  Every bin is written once, by one unit: the same bits for any slab and any order of the
+ * units.  Stream-ordered; no two calls on one handle may overlap.  PHK_EINVAL, before anything is enqueued, for a NULL handle,
+ * NULL params / inds / ll, bin < 1, W outside [0, L], NULL track with W < L. */
+int phk_predictive(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* track,
+                   void* stream);
+
 /* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
  * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
  * precedes site 0, site t is step t + 1, a missing site has e = 1):

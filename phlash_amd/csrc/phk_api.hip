@@ -22,6 +22,7 @@
 #include "viterbi_args.h"
 #include "sample_args.h"
 #include "trans_args.h"
+#include "loo_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -33,7 +34,8 @@ namespace phk {
     hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);                   \
     hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);                \
-    hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_loo_##tag(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -1005,9 +1007,10 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
     if (word & phk::FLAG_OVERRUN) {
         static const char* const names[] = {"?", "fwd_kernel", "bwd_kernel (serial sweep)", "bwd_kernel (segment sweep)", "bscan_kernel",
                                             "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel",
-                                            "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)"};
+                                            "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)",
+                                            "loo_kernel (serial sweep)", "loo_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 11 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 13 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1462,13 +1465,16 @@ struct TransOut {
     const int64_t* lens;
     void* arrivals;
     void* changes;
+    void* track;  // phk_predictive: the predictive sweep (launch_loo.hip) runs instead, arrivals and changes are unused
+    bool loo;
 };
 
 // Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
 // call of this shape would run, then the decode sweep instead of the gradient sweep.  The plan is read, never tuned or recorded:
 // decoding leaves the autotune cache and everything a gradient call decides unchanged.
 // tr != nullptr (phk_transitions): the same legs, slabs and stream ordering with the transition sweep (launch_trans.hip) in the
-// decode sweep's place; values, mean and marginals are unused then.
+// decode sweep's place; values, mean and marginals are unused then.  tr->loo (phk_predictive): the leave-one-out predictive sweep
+// (launch_loo.hip) in that place.
 static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                           const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                           double* ll, void* mean, void* marginals, void* stream, const TransOut* tr = nullptr) {
@@ -1476,7 +1482,8 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
     if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
     // (W = L: no scored site, nbin = 0, ll = 0 -- the outputs are empty, and an empty device buffer may well be a null pointer)
-    if (tr && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
+    if (tr && tr->loo && !tr->track && W < h->L) return fail(PHK_EINVAL, "track is NULL: nothing to compute");
+    if (tr && !tr->loo && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
     if (!tr && !mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
@@ -1498,6 +1505,14 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     case k: trn = h->dbl ? phk::launch_trans_f64_##k : phk::launch_trans_f32_##k; break;
     switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
 #undef PHK_CASE
+    typedef hipError_t (*loo_fn)(int, int, const phk::KArgs&, const phk::LArgs&, int, int, hipStream_t);
+    loo_fn loo = nullptr;
+#define PHK_CASE(k) \
+    case k: loo = h->dbl ? phk::launch_loo_f64_##k : phk::launch_loo_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    const bool is_loo = tr && tr->loo;
+    const char* const sweep_name = is_loo ? "predictive" : (tr ? "transition" : "decode");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
@@ -1600,12 +1615,17 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             t.lens = tr ? tr->lens : nullptr;
             t.arr = tr && tr->arrivals ? (char*)tr->arrivals + (size_t)((b0 * S + s0) * nbin * 3 * K) * rs : nullptr;
             t.chg = tr && tr->changes ? (char*)tr->changes + (size_t)((b0 * S + s0) * nbin * 2) * rs : nullptr;
+            phk::LArgs lo;
+            lo.bin = bin;
+            lo.nbin = nbin;
+            lo.lens = tr ? tr->lens : nullptr;
+            lo.track = is_loo && tr->track ? (char*)tr->track + (size_t)((b0 * S + s0) * nbin * 3) * rs : nullptr;
             hipError_t e;
             if (!plan.segmented) {
                 e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-                e = tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
-                if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", tr ? "transition" : "decode", K, plan.T, hipGetErrorString(e));
+                e = is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", sweep_name, K, plan.T, hipGetErrorString(e));
                 continue;
             }
             // segmented: forward kernel || beta scan (second stream), then the decode units
@@ -1617,9 +1637,8 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
             HIP_TRY(hipEventRecord(h->ev_join, h->side));
             HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            e = tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
-            if (e != hipSuccess)
-                return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", tr ? "transition" : "decode", K, plan.T, units, hipGetErrorString(e));
+            e = is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", sweep_name, K, plan.T, units, hipGetErrorString(e));
         }
     }
     return PHK_OK;
@@ -1634,7 +1653,14 @@ int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t 
 int phk_transitions(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* arrivals,
                     void* changes, void* stream) {
-    const TransOut tr = {lens, arrivals, changes};
+    const TransOut tr = {lens, arrivals, changes, nullptr, false};
+    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+}
+
+int phk_predictive(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* track,
+                   void* stream) {
+    const TransOut tr = {lens, nullptr, nullptr, track, true};
     return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
 }
 

@@ -4,8 +4,9 @@ paths drawn from the posterior.
 
 The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.posterior`` -> ``phk_posterior``), the paths
 from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sampling traceback (``PSMCKernel.sample_paths`` ->
-``phk_sample_paths``); this module only builds the models, pads ragged
-inputs, averages and run-length encodes.  There is no CPU path.
+``phk_sample_paths``), the breakpoint track from its transition sweep (``PSMCKernel.transitions`` -> ``phk_transitions``) and
+the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``); this
+module only builds the models, pads ragged inputs, averages, counts and run-length encodes.  There is no CPU path.
 """
 
 from __future__ import annotations
@@ -115,6 +116,61 @@ def posterior_changes(dms, data, window_size: int = 100, bin: int = 1, device=No
                       for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
     out = kern.transitions(pp, torch.arange(rows.shape[0], device=dev), bin=bin, lens=lens, arrivals=False)
     track = out.changes.to(torch.float64).mean(0)  # [N, nbin, 2]: equal weight per model
+    if spans is None:
+        return track
+    return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
+def predictive_check(dms, data, window_size: int = 100, bin: int = 1, device=None, double_precision: bool = False):
+    """Leave-one-out check of a size history along the genome, per bin of ``bin`` windows, for every row of ``data``: what the
+    model expects of each window given all the others, beside what the data has.
+
+    For each bin five numbers: (expected het windows among the observed ones, imputed het windows among the missing ones, the
+    leave-one-out log score, observed het windows, observed windows).  The first three are bin sums of phet_t = P(window t is
+    het | every other window of the row) over the observed windows, of the same over the missing windows, and of
+    log P(o_t | o_{-t}) over the observed windows, exact (``PSMCKernel.predictive``); the last two are counted from ``data``
+    on the host.  Where the first runs far from the fourth the model predicts the data badly; the second is the imputation
+    under an accessibility mask.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.  The first
+        three numbers are averaged over the models with equal weight.  The mean over models of per-model leave-one-out terms
+        is NOT the leave-one-out predictive of the mixture of the models: that one averages phet_t per site before the log is
+        taken, which this function does not do.
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, and the padded windows count nothing (each
+        row's own length goes to the kernel, which masks them: a padded window would otherwise be imputed).
+    Returns float64 [N, ceil(L / bin), 5] on the device for a matrix, a list of such tensors (one per contig) for a list.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.predictive(pp, torch.arange(rows.shape[0], device=dev), bin=bin, lens=lens)
+    model = torch.stack([out.het_observed, out.het_missing, out.score], -1).to(torch.float64).mean(0)  # [N, nbin, 3]
+    # the data's own counts per bin (padding is missing: it counts nothing)
+    N, L = rows.shape
+    nbin = (L + bin - 1) // bin
+    padded = np.full((N, nbin * bin), -1, dtype=np.int8)
+    padded[:, :L] = rows
+    padded = padded.reshape(N, nbin, bin)
+    own = np.stack([(padded >= 1).sum(-1), (padded >= 0).sum(-1)], -1).astype(np.float64)
+    track = torch.cat([model, torch.as_tensor(own, device=dev)], -1)  # [N, nbin, 5]
     if spans is None:
         return track
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]

@@ -72,6 +72,16 @@ def _transitions_guarded(kern, *args, **kw):
     return out
 
 
+def _predictive_guarded(kern, *args, **kw):
+    """engine.predictive with the same safety net as ``_run_guarded`` (the predictive sweep raises the same underflow flag)."""
+    out = kern._eng.predictive(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.predictive(*args, **kw)
+    return out
+
+
 def _viterbi_guarded(kern, *args, **kw):
     """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
     out = kern._eng.viterbi(*args, **kw)
@@ -106,6 +116,16 @@ class Transitions(NamedTuple):
     ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
     changes: torch.Tensor  # [..., nbin, 2]: bin sums of the expected moves to an older / a younger state
     arrivals: torch.Tensor | None  # [..., nbin, 3, M]: bin means of (stay, up, down) per state, or None
+
+
+class Predictive(NamedTuple):
+    """What ``PSMCKernel.predictive`` returns (device tensors, batch dims stripped as ``loglik`` strips them; the last three are
+    views of one track)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    het_observed: torch.Tensor  # [..., nbin]: bin sums of P(o_t = het | o_{-t}) over the observed sites
+    het_missing: torch.Tensor  # [..., nbin]: the same over the missing sites
+    score: torch.Tensor  # [..., nbin]: bin sums of log P(o_t | o_{-t}) over the observed sites
 
 
 class Viterbi(NamedTuple):
@@ -328,6 +348,31 @@ class PSMCKernel:
             ll, c, a = _transitions_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens, arrivals=bool(arrivals))
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Transitions(strip(ll), strip(c), strip(a))
+
+    # ---- leave-one-out predictive -------------------------------------------------------------
+    def predictive(self, pp, index, *, bin: int = 1, lens=None) -> Predictive:
+        """What the rest of a row says about each of its sites: phet_t = P(o_t = het | o_{-t}), the probability that scored
+        site t is het given every other site of the row (and that it is observed at all), as sums over bins of ``bin`` scored
+        sites.  ``het_observed`` [..., nbin] sums phet_t over the bin's observed sites -- the expected number of het windows,
+        to be held against the observed count -- ``het_missing`` sums it over the missing sites -- the imputed het count under
+        the mask -- and ``score`` sums log P(o_t | o_{-t}) over the observed sites, the leave-one-out log score (missing sites
+        add 0).  Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as ``loglik``); nbin =
+        ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <=
+        L``): sites at or past a row's own length add nothing.  Returns ``Predictive(ll, het_observed, het_missing, score)``,
+        device tensors in ``float_type`` (ll float64); no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            ll, track = _predictive_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens)
+        track = self._strip(track, added_B, added_S)
+        return Predictive(self._strip(ll, added_B, added_S), track[..., 0], track[..., 1], track[..., 2])
 
     # ---- Viterbi decoding ---------------------------------------------------------------------
     def viterbi(self, pp, index, *, lens=None) -> Viterbi:
