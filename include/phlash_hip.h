@@ -201,6 +201,38 @@ int phk_predictive(phk_handle* h, const void* params, int64_t pstride_b, int64_t
                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* track,
                    void* stream);
 
+/* Tract posteriors (the reference has no counterpart): for every bin of scored sites of each sequence (b, s), the posterior
+ * expectation of the product of a per-state weight over the bin's sites -- with the weight an indicator of a state set S, the
+ * probability that EVERY site of the bin has its state in S: a joint event of the bin's sites, which the per-site marginals do
+ * not determine (their bin mean is only an upper bound).  Conventions of phk_posterior and phk_predictive: z_0 ~ pi precedes
+ * site 0, alpha_t is the forward vector after site t with alpha_{-1} = pi, beta_{L-1} = 1 and beta_t holds the emissions of sites
+ * t+1 .. L-1 only, a missing site has e = 1, the W warm-up sites are conditioned on and not reported, and there is no warm-up
+ * correction.  Let m in [0,1]^K be the particle's weight row.  Bin k holds the scored sites s = W + k bin .. e =
+ * min(s + bin, L) - 1 (the last bin may be partial; nbin = ceil((L - W) / bin)), and
+ *   q_e     = beta_e
+ *   q_{t-1} = A (m .* e_{o_t} .* q_t)            for t = e, e-1, .., s
+ *   tract_k = sum_i alpha_{s-1}(i) q_{s-1}(i) / sum_i alpha_{s-1}(i) beta_{s-1}(i)
+ *           = E[ prod_{t=s..e} m(z_t) | o ]       ( = P(z_s .. z_e in S | o) for an indicator of S ).
+ *   weights    device double [B, K] with row stride wstride_b, or [K] with wstride_b = 0 (one row for all particles, like
+ *              `values` of phk_posterior); rounded to the handle's float type; values outside [0, 1] are the caller's error;
+ *   tract      [B, S, nbin] in the handle's float type;
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N] or NULL: a site at or past its row's own length is stepped with m replaced by 1, so it restricts
+ *              nothing; a bin without a site of the row's own is written as 0; an entry outside (W, L] is clamped and raises
+ *              the bad-index flag.
+ * q runs on beta's scale and q <= beta holds elementwise in the computed numbers as well, so a tract never exceeds 1 and a
+ * smaller set never has the larger tract.  A bin whose denominator is not positive is written as 0 and raises the underflow flag
+ * (re-evaluate after phk_set_rescale_interval(h, 1)); a numerator that flushes to 0 is a legitimate answer (q can underflow
+ * where beta does not) and raises nothing.  With W = L there is no scored site: nbin = 0, ll = 0, tract is empty and may be NULL.
+ * params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs, slabs
+ * (phk_set_workspace_limit) and stream ordering are phk_posterior's, with the tract sweep in the decode sweep's place; the plan is
+ * read, never tuned or recorded.  Every bin is written once, by one unit: the same bits for any slab and any order of the units.
+ * Stream-ordered; no two calls on one handle may overlap.  PHK_EINVAL, before anything is enqueued, for a NULL handle, NULL
+ * params / inds / ll / weights, bin < 1, W outside [0, L], NULL tract with W < L. */
+int phk_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+               const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* weights,
+               int64_t wstride_b, const int64_t* lens, double* ll, void* tract, void* stream);
+
 /* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
  * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
  * precedes site 0, site t is step t + 1, a missing site has e = 1):

@@ -29,7 +29,7 @@ def __getattr__(name):
     if name == "posterior_tmrca":
         from .decode import posterior_tmrca
         return posterior_tmrca
-    if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check"):
+    if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check", "tract_posterior"):
         from . import decode
         return getattr(decode, name)
     if name == "RawContig":

@@ -5,8 +5,9 @@ paths drawn from the posterior.
 The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.posterior`` -> ``phk_posterior``), the paths
 from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sampling traceback (``PSMCKernel.sample_paths`` ->
 ``phk_sample_paths``), the breakpoint track from its transition sweep (``PSMCKernel.transitions`` -> ``phk_transitions``) and
-the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``); this
-module only builds the models, pads ragged inputs, averages, counts and run-length encodes.  There is no CPU path.
+the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``) and the
+tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``); this module only builds the models, pads
+ragged inputs, averages, counts and run-length encodes.  There is no CPU path.
 """
 
 from __future__ import annotations
@@ -171,6 +172,63 @@ def predictive_check(dms, data, window_size: int = 100, bin: int = 1, device=Non
     padded = padded.reshape(N, nbin, bin)
     own = np.stack([(padded >= 1).sum(-1), (padded >= 0).sum(-1)], -1).astype(np.float64)
     track = torch.cat([model, torch.as_tensor(own, device=dev)], -1)  # [N, nbin, 5]
+    if spans is None:
+        return track
+    return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
+def tract_posterior(dms, data, t_max, t_min: float = 0.0, window_size: int = 100, bin: int = 1, weights=None, device=None,
+                    double_precision: bool = False):
+    """Posterior probability that the TMRCA of EVERY window of a bin of ``bin`` windows lies in [t_min, t_max), for every row of
+    ``data``: where the tracts are (``t_max`` small: runs of homozygosity and IBD segments; ``t_min`` large: deep-coalescence
+    deserts).  The event is joint over the bin's windows and the probability is exact (``PSMCKernel.tracts``): the bin mean of the
+    per-window marginals is only an upper bound of it, and sampled paths only estimate it.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.  For each model,
+        state k covers [eta.t[k], eta.t[k + 1]), the last one open, in the model's own time unit (that of ``eta.ect()``:
+        generations when ``fit`` was given ``mutation_rate``); the state counts as inside when its whole interval lies inside
+        [t_min, t_max).  The probabilities are averaged over the models with equal weight, and this mean IS the posterior
+        probability of the event under the equal-weight mixture of the models: a probability given the data is linear in the
+        mixture's components (unlike the leave-one-out terms of ``predictive_check``).
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, and the padded windows restrict nothing (each
+        row's own length goes to the kernel, which masks them).
+    weights: [M] or [len(dms), M] in [0, 1], overriding the time range: the result is then E[prod of weights(z_t) over the
+        bin's windows | data].
+    Returns float64 [N, ceil(L / bin)] on the device for a matrix, a list of such tensors (one per contig) for a list.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if weights is None:
+        assert float(t_min) < float(t_max), "the TMRCA range [t_min, t_max) is empty"
+        w = np.empty((len(dms), M))
+        for i, dm in enumerate(dms):
+            t = np.asarray(torch.as_tensor(dm.eta.t, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(M)
+            lo, hi = t, np.append(t[1:], np.inf)
+            w[i] = (lo >= float(t_min)) & (hi <= float(t_max))
+    else:
+        w = np.asarray(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
+        assert w.shape in ((M,), (len(dms), M)), f"weights: [{M}] or [{len(dms)}, {M}]"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.tracts(pp, torch.arange(rows.shape[0], device=dev), weights=w, bin=bin, lens=lens)
+    track = out.prob.to(torch.float64).mean(0)  # [N, nbin]: equal weight per model
     if spans is None:
         return track
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]

@@ -372,6 +372,55 @@ class HipEngine:
         _lib.check(rc)
         return ll, track
 
+    def tracts(self, params: torch.Tensor, inds: torch.Tensor, weights: torch.Tensor, warmup: int = 0, bin: int = 1,
+               lens: torch.Tensor | None = None):
+        """Tract posteriors (``phk_tracts``): params / inds as ``run``.  ``weights``: float64 [B, K] or [K] on the device, the
+        per-state weight m in [0, 1] (an indicator of a state set for a tract probability).  Returns (ll [B, S] float64, tract
+        [B, S, nbin] in the handle's float type) over bins of ``bin`` scored sites (nbin = ceil((L - warmup) / bin)): per bin
+        E[prod of m(z_t) over the bin's sites | o], for an indicator the posterior probability that every site of the bin has
+        its state in the set.  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
+        L``): a site at or past a row's own length restricts nothing, a bin without a site of the row's own is 0."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        assert weights.is_cuda and weights.device == self.device and weights.dtype == torch.float64, "weights: float64 on the device"
+        assert weights.shape in ((self.K_user,), (B, self.K_user)), f"weights: [K] or [B, K], got {tuple(weights.shape)}"
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+            weights = torch.cat([weights, torch.zeros(weights.shape[:-1] + (pad_k,), dtype=weights.dtype, device=weights.device)], -1)
+        weights = weights.contiguous()
+        if lens is not None:
+            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
+            lens = lens.contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pf = None
+        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
+            p64 = params.contiguous()
+            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
+                                               None, ctypes.c_void_p(stream)))
+        else:
+            p = params.to(self.dtype).contiguous()
+        inds = inds.contiguous()
+        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        tract = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device)
+        rc = _lib.load().phk_tracts(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            inds.data_ptr(), B, S, int(warmup), int(bin), weights.data_ptr(), self.K if weights.ndim == 2 else 0,
+            lens.data_ptr() if lens is not None else None, ll.data_ptr(), tract.data_ptr() if nbin > 0 else None,
+            ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        return ll, tract
+
     def viterbi(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, lens: torch.Tensor | None = None):
         """Viterbi decoding (``phk_viterbi``): params / inds as ``run``.  Returns (logp [B, S] float64, path [B, S, L - warmup]
         uint8): the log probability of the single most probable hidden path of every sequence and its states at the sites

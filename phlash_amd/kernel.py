@@ -82,6 +82,16 @@ def _predictive_guarded(kern, *args, **kw):
     return out
 
 
+def _tracts_guarded(kern, *args, **kw):
+    """engine.tracts with the same safety net as ``_run_guarded`` (the tract sweep raises the same underflow flag)."""
+    out = kern._eng.tracts(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.tracts(*args, **kw)
+    return out
+
+
 def _viterbi_guarded(kern, *args, **kw):
     """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
     out = kern._eng.viterbi(*args, **kw)
@@ -126,6 +136,13 @@ class Predictive(NamedTuple):
     het_observed: torch.Tensor  # [..., nbin]: bin sums of P(o_t = het | o_{-t}) over the observed sites
     het_missing: torch.Tensor  # [..., nbin]: the same over the missing sites
     score: torch.Tensor  # [..., nbin]: bin sums of log P(o_t | o_{-t}) over the observed sites
+
+
+class Tracts(NamedTuple):
+    """What ``PSMCKernel.tracts`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    prob: torch.Tensor  # [..., nbin]: E[prod of weights(z_t) over the bin's sites | o]
 
 
 class Viterbi(NamedTuple):
@@ -373,6 +390,33 @@ class PSMCKernel:
             ll, track = _predictive_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens)
         track = self._strip(track, added_B, added_S)
         return Predictive(self._strip(ll, added_B, added_S), track[..., 0], track[..., 1], track[..., 2])
+
+    # ---- tract posteriors -----------------------------------------------------------------------
+    def tracts(self, pp, index, *, weights, bin: int = 1, lens=None) -> Tracts:
+        """Where the tracts are: for every bin of ``bin`` scored sites, ``prob`` = E[prod over the bin's sites of
+        weights(z_t) | o].  With ``weights`` the indicator of a set of states this is the posterior probability that EVERY site of
+        the bin has its state in the set -- a joint event of the bin's sites, exact, which neither the per-site marginals (their
+        bin mean is only an upper bound) nor sampled paths (an estimate) give.  ``weights``: [M], or [B, M] with one row per
+        particle of ``pp``, values in [0, 1].  Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as
+        ``loglik``); nbin = ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data,
+        ``overlap < len <= L``): a site at or past a row's own length restricts nothing, and a bin without a site of the row's
+        own is 0.  Returns ``Tracts(ll, prob)``, device tensors in ``float_type`` (ll float64); no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            w = torch.as_tensor(np.array(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64),
+                                dtype=torch.float64, device=self.device)
+            assert w.shape in ((self.M,), (pa.shape[0], self.M)), f"weights: [{self.M}] or [{pa.shape[0]}, {self.M}], got {tuple(w.shape)}"
+            assert bool(((w >= 0) & (w <= 1)).all()), "weights must lie in [0, 1]"
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            ll, tract = _tracts_guarded(self, pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
+        return Tracts(self._strip(ll, added_B, added_S), self._strip(tract, added_B, added_S))
 
     # ---- Viterbi decoding ---------------------------------------------------------------------
     def viterbi(self, pp, index, *, lens=None) -> Viterbi:

@@ -1,0 +1,106 @@
+"""HIP-event time of a tract-posterior call (bin = 1 and bin = 100) against a posterior-decoding call (mean track, same bin) on
+the same inputs, K = 16, float32 kernels (not run by bench.py).
+
+Shapes: (b) 100 models x 20 rows x 100,000 windows; (c) the reference's production shape, 500 x 5 x 100,000; both at 5 % hets.
+Before it reports a shape the script checks the tracts against the float64 dense oracle of tests/tract_oracle.py on two
+(model, row) pairs, and prints one JSON line per shape and bin with the library's sha256.
+
+    python scripts/tract_timing.py [--shapes bc] [--bins 1,100] [--reps 5]
+"""
+
+from __future__ import annotations
+
+import argparse
+import hashlib
+import json
+import os
+import sys
+
+import numpy as np
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+sys.path.insert(0, os.path.join(ROOT, "tests"))
+
+SHAPES = {"b": (100, 20, 100_000, 0.05), "c": (500, 5, 100_000, 0.05)}
+
+
+def rows(S, L, het, seed):
+    g = np.random.default_rng(seed)
+    d = (g.random((S, L), dtype=np.float32) < het).astype(np.int8)
+    d.flat[g.integers(0, d.size, size=int(0.01 * d.size))] = -1
+    d[:, 0] = 1
+    return d
+
+
+def timed_pair(f, g, reps):
+    """medians (ms) of ``reps`` alternating calls of f and g after one warm-up call of each"""
+    f()
+    g()
+    torch.cuda.synchronize()
+    tf, tg = [], []
+    for _ in range(reps):
+        for fn, ts in ((f, tf), (g, tg)):
+            e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+            e0.record()
+            fn()
+            e1.record()
+            torch.cuda.synchronize()
+            ts.append(e0.elapsed_time(e1))
+    return float(np.median(tf)), float(np.median(tg))
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--shapes", default="bc")
+    ap.add_argument("--bins", default="1,100")
+    ap.add_argument("--reps", type=int, default=5)
+    args = ap.parse_args()
+    from phlash_amd import _lib
+    from phlash_amd.engine import HipEngine
+    from phlash_amd.params import PSMCParams
+    from phlash_amd.synth import particle_population
+    import tract_bars as bars
+    import tract_oracle as to
+    from oracle import psmc_numpy as pn
+
+    sha = hashlib.sha256(open(_lib.LIB_PATH, "rb").read()).hexdigest()
+    m = (np.arange(16) < 11).astype(np.float64)  # the eleven youngest states
+    for key in args.shapes:
+        B, S, L, het = SHAPES[key]
+        data = rows(S, L, het, seed=7)
+        tmpl, x = particle_population(16, B, seed=1, sigma=0.25)
+        dm = tmpl.from_flat(x).to_dm()
+        pp = PSMCParams.from_dm(dm)
+        P = pp.stack()[:, None].cuda()  # [B, 1, 7, K] float64
+        f = torch.as_tensor(dm.eta.ect(), dtype=torch.float64).reshape(-1, 16).expand(B, 16).contiguous().cuda()
+        w = torch.as_tensor(m).cuda()
+        eng = HipEngine(16, data, double_precision=False)
+        inds = torch.arange(S, device="cuda")
+        for bin in (int(b) for b in args.bins.split(",")):
+            ll, trk = eng.tracts(P, inds, w, 0, bin=bin)
+            assert not eng.underflow_risk()
+            assert torch.isfinite(trk).all()
+            ll0, _, _ = eng.posterior(P, inds, 0, values=f, bin=bin, marginals=False, mean=True)
+            assert torch.equal(ll, ll0)
+            worst = 0.0
+            for b, s in ((0, 0), (B - 1, S - 1)):
+                q = pn.PP(*(getattr(pp, name)[b].numpy() for name in pn.PP._fields))
+                ref, llr = to.dense(q, data[s], m, 0, bin)
+                worst = max(worst, float(np.abs(trk[b, s].double().cpu().numpy() - ref).max()))
+                assert abs(float(ll[b, s]) / llr - 1) < 1e-5
+            assert worst < bars.F32_TRACT_BAR, worst
+            check = f"tract vs float64 oracle on 2 sequences: max abs {worst:.1e} (mean tract {float(trk.mean()):.3f}); ll bitwise phk_posterior's"
+            t_tr, t_dec = timed_pair(lambda: eng.tracts(P, inds, w, 0, bin=bin),
+                                     lambda: eng.posterior(P, inds, 0, values=f, bin=bin, marginals=False, mean=True), args.reps)
+            print(json.dumps({"shape": key, "B": B, "S": S, "L": L, "het": het, "bin": bin, "tracts_ms": round(t_tr, 3),
+                              "posterior_ms": round(t_dec, 3), "ratio": round(t_tr / t_dec, 3), "plan": eng.get_plan(), "check": check,
+                              "lib_sha256": sha}), flush=True)
+            del trk, ll
+        del eng
+        torch.cuda.empty_cache()
+
+
+if __name__ == "__main__":
+    main()
