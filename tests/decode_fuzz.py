@@ -112,8 +112,13 @@ class Draw(types.SimpleNamespace):
         return s + f" lens={None if self.lens is None else self.lens.tolist()}"
 
 
-def _draw(seed, kind, force_dbl):
-    rng = np.random.default_rng([20_000 + seed, 0 if kind == "posterior" else 1])
+STREAMS = {"posterior": 0, "viterbi": 1, "transitions": 2, "predictive": 3, "tracts": 4}  # a random stream per kind
+
+
+def _draw(seed, kind, force_dbl, with_rng=False):
+    """Every kind but "viterbi" takes the posterior draw (the sweeps of tests/sweep_fuzz.py are dispatched as phk_posterior is);
+    ``with_rng``: -> (draw, its generator), for a caller that draws more fields after these."""
+    rng = np.random.default_rng([20_000 + seed, STREAMS[kind]])
     d = Draw(seed=seed, kind=kind, redrawn=False)
     # K x float type and the row length are stratified: every cell of the lists comes up within 20 resp. 16 seeds
     d.K = KS[seed % 10]
@@ -123,12 +128,12 @@ def _draw(seed, kind, force_dbl):
     d.B, d.S = int(rng.integers(1, 5)), int(rng.integers(1, 7))
     d.N = int(rng.integers(d.S, d.S + 5))
     d.inds = rng.integers(0, d.N, size=d.S)
-    wmax = L if kind == "posterior" else L - 1
+    wmax = L - 1 if kind == "viterbi" else L
     d.W = int(rng.integers(0, wmax + 1)) if rng.integers(2) else 0
     edge = int(rng.integers(12))
     if edge == 0:
         d.W = L - 1
-    elif edge == 1 and kind == "posterior":
+    elif edge == 1 and kind != "viterbi":
         d.W = L
     d.het = float(HETS[rng.integers(4)])
     d.miss = float(MISSES[rng.integers(3)])
@@ -208,7 +213,7 @@ def _draw(seed, kind, force_dbl):
     elif vform == 2:
         d.values = np.cumsum(rng.uniform(0.05, 1.0, size=(d.B, d.K)), axis=1) * rng.uniform(0.2, 5.0, size=(d.B, 1))
     d.marginals = bool(rng.integers(2)) or d.values is None
-    return d
+    return (d, rng) if with_rng else d
 
 
 @functools.lru_cache(maxsize=None)
