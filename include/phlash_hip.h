@@ -410,6 +410,12 @@ int phk_underflow_risk(phk_handle* h, int* flag);
  * kernel, bit 1 backward kernel, bit 2 beta scan.  A scale below ~1/2 makes a healthy evaluation overrun, which is how
  * tests/test_plans_and_modes.py exercises the PHK_EOVERRUN path. */
 int phk_set_loop_budget_scale(phk_handle* h, int kernels, int num, int den);
+/* Test hook (synchronises): of the checkpoint blocks the forward kernel wrote in the last launch of the last gradient call, how
+ * many per sequence carry a non-zero exponent, i.e. had a power of two taken out of the state inside them.  counts[i], i < min(n,
+ * sequences of that launch), in the launch's storage order; *blocks = checkpoint blocks per sequence.  The forward kernels with
+ * several states per lane rescale on demand at the default interval (a sequence only once its mass has fallen below 2^-16), so
+ * nearly every block of an ordinary row counts 0 there; tests/test_rescale_on_demand.py reads how often the rescale fired. */
+int phk_block_rescale_counts(phk_handle* h, int64_t* counts, int64_t n, int64_t* blocks);
 /* Developer builds (-DPHK_ASM_RUN=1) only: the K = 16 float32 sweeps with two lanes per sequence run their hot blocks through a
  * hand-written instruction sequence (csrc/sweep_run_k16r2.inc, generated by scripts/gen_sweep_asm.py: the C++ body's arithmetic,
  * operation for operation, an all-hom block without its per-site tests) when on = 1.  It returns the same bits as the C++ body

@@ -34,6 +34,12 @@
     const real* pfb = prefold_block<real>(A, bb, ss);
     const bool fold_seq = lane.try_fold(pfb != nullptr ? pfb + rank * L::SPL : nullptr);  // (float32: the folded model, see Lane::try_fold)
     constexpr bool DENSE = has_dense<real, K, R>() && NRM == 4;  // hom-run operators (see dense16)
+    // Several states per lane, NRM = 4: the full blocks (straight_block, fold_block) rescale on demand -- the rescale
+    // sites of the schedule only test the sum the site's own scan has produced, and a sequence is rescaled once it
+    // has lost 2^-PHK_RESCALE_TRIGGER_EXP (Lane::rescale_on_demand).  Most blocks record an exponent of 0; E, eblk, eseg
+    // and eb_min stay "the exponent actually removed".  The partial last block and the warm-up block keep the fixed
+    // schedule, NRM = 1 and 2 keep theirs bit for bit, and the one-state-per-lane kernels rescale by debt (dense_block).
+    constexpr bool ONDEMAND = NRM == 4 && SPL > 1 && PHK_RESCALE_TRIGGER_EXP > 0;
     if constexpr (DENSE)
         lane.template load_dense<T == 16>(A.ops_f + (A.pstride_s != 0 ? bb * A.S + ss : bb) * DENSE_OPS_FLOATS, rank, fold_seq,
                                           PHK_KERNEL_MR ? (float*)smem_raw + (size_t)blockDim.x * L::ETAB_STRIDE + (size_t)threadIdx.x * DENSE_Q8_STRIDE : nullptr);
@@ -234,9 +240,19 @@
             V en[NP];
             if (i + 1 < T) lane.emis((codes >> (2 * (i + 1))) & 3, en);
             real sc;
-            const int ex = lane.fwd_site(a, ec, sc, rescale_after<NRM>(i));
-            E += ex;
-            if (NRM > 1 && rescale_after<NRM>(i)) ex_slack = min(ex_slack, ex - RISK_EXP);
+            if constexpr (ONDEMAND) {
+                if (rescale_after<NRM>(i)) {
+                    real sum_before;
+                    lane.fwd_site_sum(a, ec, sum_before);
+                    lane.template rescale_on_demand<RISK_EXP>(a, sum_before, E, ex_slack);
+                } else {
+                    lane.fwd_site(a, ec, sc, false);
+                }
+            } else {
+                const int ex = lane.fwd_site(a, ec, sc, rescale_after<NRM>(i));
+                E += ex;
+                if (NRM > 1 && rescale_after<NRM>(i)) ex_slack = min(ex_slack, ex - RISK_EXP);
+            }
             if (i + 1 < T) {
 #pragma unroll
                 for (int h = 0; h < NP; ++h) ec[h] = en[h];
@@ -327,7 +343,13 @@
         for (int i = 0; i < T; ++i) {
             V none[NP];
             real sc;
-            lane.template fwd_site<false>(a, none, sc, false);
+            [[maybe_unused]] real sum_before = real(0);  // (ONDEMAND: of the state entering the site, for the test behind it)
+            if constexpr (ONDEMAND) {
+                if (rescale_after<NRM>(i)) lane.template fwd_site_sum<false>(a, none, sum_before);
+                else lane.template fwd_site<false>(a, none, sc, false);
+            } else {
+                lane.template fwd_site<false>(a, none, sc, false);
+            }
             if constexpr (FREG) {
                 // round 6: the two ratio rows in registers, het / missing lanes multiply under the exec mask behind one
                 // wave-uniform bit each (round 5: the lane's row from the LDS table, a round trip a lone wave cannot hide)
@@ -352,9 +374,13 @@
                 for (int h = 0; h < NP; ++h) a[h] = a[h] * e[h];
             }
             if (rescale_after<NRM>(i)) {
-                const int ex = lane.rescale(a);
-                E += ex;
-                if (NRM > 1) ex_slack = min(ex_slack, ex - RISK_EXP);
+                if constexpr (ONDEMAND) {
+                    lane.template rescale_on_demand<RISK_EXP>(a, sum_before, E, ex_slack);
+                } else {
+                    const int ex = lane.rescale(a);
+                    E += ex;
+                    if (NRM > 1) ex_slack = min(ex_slack, ex - RISK_EXP);
+                }
             }
 #if PHK_FWD_SITE_BARRIER
             __builtin_amdgcn_sched_barrier(0);

@@ -162,6 +162,7 @@ struct phk_handle {
     hipStream_t last_stream = nullptr;  // stream of the last phk_loglik (the flag word is read behind it)
     std::map<std::pair<int64_t, int>, Plan> tuned;  // (sequences per launch, grad?) -> plan
     int64_t last_Bs = 0, last_Ss = 0;  // particle x chunk slab of the last phk_loglik
+    int64_t eblk_nseq = 0, eblk_nblk = 0;  // shape of the block exponents the last gradient launch left in eblk
     int64_t last_total = -1;  // B*S of the last phk_loglik and the plan it ran with
     Plan last_plan;
     hipStream_t side = nullptr;  // second stream of the segmented plan
@@ -466,6 +467,8 @@ int enqueue(phk_handle* h, const Launchers& l, phk::KArgs a, const Plan& plan, b
         if (e_mid) HIP_TRY(hipEventRecord(e_mid, st));
         return PHK_OK;
     }
+    h->eblk_nseq = nseq;  // what the forward kernel of this launch leaves in eblk: [blocks][nseq] (phk_block_rescale_counts)
+    h->eblk_nblk = (h->L + plan.T - 1) / plan.T;
     if (!h->dbl || plan.segmented) HIP_TRY(hipMemsetAsync(h->gacc.p, 0, (size_t)nseq * 6 * K * sizeof(double), st));
     if (!plan.segmented && plan.hybrid_first > 0 && plan.hybrid_first < nseq && n_units(h, plan.T, a.W) >= 2) {
         // hybrid: forward kernel over everything || beta scan over the tail range; then the serial
@@ -1064,6 +1067,23 @@ int phk_get_slab(phk_handle* h, int64_t* particles, int64_t* chunks) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
     if (particles) *particles = h->last_Bs;
     if (chunks) *chunks = h->last_Ss;
+    return PHK_OK;
+}
+
+int phk_block_rescale_counts(phk_handle* h, int64_t* counts, int64_t n, int64_t* blocks) {
+    if (!h || !counts || n < 0) return fail(PHK_EINVAL, "NULL argument");
+    if (blocks) *blocks = h->eblk_nblk;
+    const int64_t nseq = h->eblk_nseq, nblk = h->eblk_nblk;
+    if (nseq <= 0 || nblk <= 0 || !h->eblk.p) return fail(PHK_EINVAL, "no gradient call has run on this handle");
+    if ((size_t)(nseq * nblk) * sizeof(int16_t) > h->eblk.cap) return fail(PHK_EINVAL, "block exponents out of range");
+    HIP_TRY(hipSetDevice(h->device));
+    HIP_TRY(hipDeviceSynchronize());
+    std::vector<int16_t> e((size_t)(nseq * nblk));
+    HIP_TRY(hipMemcpy(e.data(), h->eblk.p, e.size() * sizeof(int16_t), hipMemcpyDeviceToHost));
+    for (int64_t i = 0; i < std::min(n, nseq); ++i) {
+        counts[i] = 0;
+        for (int64_t b = 0; b < nblk; ++b) counts[i] += e[(size_t)(b * nseq + i)] != 0;
+    }
     return PHK_OK;
 }
 

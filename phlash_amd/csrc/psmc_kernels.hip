@@ -90,6 +90,13 @@
 #ifndef PHK_EXP_NO_CKPT_STORE
 #define PHK_EXP_NO_CKPT_STORE 0  // timing-only diagnostic builds: the forward kernel does not store its checkpoints (results are wrong)
 #endif
+#ifndef PHK_RESCALE_TRIGGER_EXP
+#define PHK_RESCALE_TRIGGER_EXP 16  // G: forward kernels with several states per lane, NRM = 4: a lane is rescaled at a rescale site only once
+                                    // its sum has fallen below 2^-G (Lane::rescale_on_demand; 0 = after every fourth site, as before)
+#endif
+#ifndef PHK_EXP_NO_BLOCK_RESCALE
+#define PHK_EXP_NO_BLOCK_RESCALE 0  // timing-only diagnostic builds: those kernels never rescale inside a full block (results are wrong)
+#endif
 #ifndef PHK_DS_FIRST
 #define PHK_DS_FIRST 0  // beta-first body: ask the scheduler to issue a site's LDS reads (next emission row, next parked w) before its arithmetic
 #endif
@@ -515,8 +522,9 @@ struct Lane : DenseOps<has_dense<real, K, R>()> {
     }
     // adjacent-pairs layout: exclusive prefix of wp.*xp into `pre` and exclusive suffix of xs (SUFW:
     // of v.*xs) into `suf`, state by state inside the lane, then the other lanes' totals
+    // (lane_sum_xs, where asked for with !SUFW: the sum of xs over this LANE's states, a by-product of the suffix scan)
     __device__ __forceinline__ void serial_scans(const V (&wp)[NP], const V (&xp)[NP], V (&pre)[NP], const V (&xs)[NP],
-                                                 V (&suf)[NP], const bool SUFW) const {
+                                                 V (&suf)[NP], const bool SUFW, real* lane_sum_xs = nullptr) const {
         real tp = real(0);
 #pragma unroll
         for (int i = 0; i < 2 * NP; ++i) {
@@ -529,6 +537,7 @@ struct Lane : DenseOps<has_dense<real, K, R>()> {
             suf[i >> 1][i & 1] = ts;
             if (i < SPL) ts = SUFW ? fma_(v[i >> 1][i & 1], xs[i >> 1][i & 1], ts) : ts + xs[i >> 1][i & 1];
         }
+        if (lane_sum_xs != nullptr) *lane_sum_xs = ts;
         if constexpr (R > 1) {
             const V cp = splat<real>(g.excl_prefix(tp));
             const V cs = splat<real>(g.excl_suffix(ts));
@@ -548,6 +557,29 @@ struct Lane : DenseOps<has_dense<real, K, R>()> {
         V tu, ta;
         half_scans<true, true>(u, x, pre_ux, tu);
         half_scans<false, false>(u, x, suf_x, ta);
+        if constexpr (R > 1 || SPL > 1) {
+            const V cu = carry<true>(tu);
+            const V ca = carry<false>(ta);
+#pragma unroll
+            for (int h = 0; h < NP; ++h) {
+                pre_ux[h] = pre_ux[h] + cu;
+                suf_x[h] = suf_x[h] + ca;
+            }
+        }
+    }
+    // The same, handing out lane_sum_x: the sum of x over this lane's states -- the suffix scan's running total, at no
+    // extra instruction (Lane::rescale_on_demand makes the sequence's sum of it).  A function of its own, like
+    // fwd_site_sum below: a pointer parameter on `scans` / `fwd_site`, null everywhere else, moved the register
+    // allocation of kernels that never ask (the split-halves forward kernels at NRM = 1: 128 -> 130 registers, 4 -> 3 waves).
+    __device__ __forceinline__ void scans_sum(const V (&x)[NP], V (&pre_ux)[NP], V (&suf_x)[NP], real& lane_sum_x) const {
+        if constexpr (!SPLIT) {
+            serial_scans(u, x, pre_ux, x, suf_x, false, &lane_sum_x);
+            return;
+        }
+        V tu, ta;
+        half_scans<true, true>(u, x, pre_ux, tu);
+        half_scans<false, false>(u, x, suf_x, ta);
+        lane_sum_x = ta[0] + ta[1];
         if constexpr (R > 1 || SPL > 1) {
             const V cu = carry<true>(tu);
             const V ca = carry<false>(ta);
@@ -861,6 +893,31 @@ struct Lane : DenseOps<has_dense<real, K, R>()> {
         for (int h = 0; h < NP; ++h) x[h] = x[h] * s2;
         return ex;
     }
+    // The same on demand (forward kernels with several states per lane, NRM = 4).  A hom site takes about 1 % of the
+    // mass, so the rescale after every fourth site multiplied by 1 or 2 nearly every time, at ~22 of a block's ~490
+    // vector instructions each.  Here the rescale site only TESTS a sum, and one that costs nothing: that of the state
+    // entering the site just stepped (lane_sum_before of fwd_site; the R lanes of a sequence add theirs up, every lane
+    // of the group gets the same bits).  A sequence whose sum has fallen below 2^-PHK_RESCALE_TRIGGER_EXP takes that
+    // sum's exponent out of x -- an exact power of two, one site stale: x lands within one site's loss of [0.5, 1) --
+    // and every other sequence multiplies by exactly 1.  The branch is wave-uniform, the decision and the scale are per
+    // sequence: what a sequence computes does not depend on its wave's other sequences.  The exponent removed (0 for
+    // the sequences that stay) is booked inside that branch -- added to E, held against 2^RISK like that of `rescale`
+    // (ex_slack: see fwd_kernel) -- so that the fall-through path is the test alone.
+    template <int RISK>
+    __device__ __forceinline__ void rescale_on_demand(V (&x)[NP], const real lane_sum_before, int& E, int& ex_slack) const {
+#if !PHK_EXP_NO_BLOCK_RESCALE
+        const real c = g.sum(lane_sum_before);
+        const bool low = c < real(1) / real(int64_t(1) << PHK_RESCALE_TRIGGER_EXP);
+        if (__builtin_expect(__any(low) != 0, 0)) {
+            const int ex = low ? frexp_exp_(c) : 0;
+            const V s2 = splat<real>(ldexp_(real(1), -ex));  // (exactly 1 where the sequence stays as it is)
+#pragma unroll
+            for (int h = 0; h < NP; ++h) x[h] = x[h] * s2;
+            E += ex;
+            ex_slack = min(ex_slack, ex - RISK);
+        }
+#endif
+    }
 
     // One forward site (hmm.py:74-79): a <- (a A) .* e_code, then, if SCALE, a *= 2^-ex with ex the
     // exponent of the sum (so that sum(a) lands in [0.5,1)); returns ex (0 if !SCALE) and the scale.
@@ -889,6 +946,20 @@ struct Lane : DenseOps<has_dense<real, K, R>()> {
         } else {
             scale = real(1);
             return 0;
+        }
+    }
+    // The same step without a rescale, handing out lane_sum_before: the sum over this lane's states of the state
+    // ENTERING the site (scans_sum), for the test of rescale_on_demand behind it.
+    template <bool EMIS = true>
+    __device__ __forceinline__ void fwd_site_sum(V (&a)[NP], const V (&e)[NP], real& lane_sum_before) const {
+        V pre[NP], suf[NP];
+        scans_sum(a, pre, suf, lane_sum_before);
+#pragma unroll
+        for (int h = 0; h < NP; ++h) {
+            V t = d[h] * a[h];
+            t = fma2<real>(v[h], pre[h], t);
+            t = fma2<real>(b[h], suf[h], t);
+            a[h] = EMIS ? t * e[h] : t;
         }
     }
 

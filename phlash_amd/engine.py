@@ -107,6 +107,17 @@ class HipEngine:
         kernel (bit 1), the beta scan (bit 2)."""
         _lib.check(_lib.load().phk_set_loop_budget_scale(self._h, int(kernels), int(num), int(den)))
 
+    def block_rescale_counts(self) -> tuple[np.ndarray, int]:
+        """Test hook (``phk_block_rescale_counts``, synchronises): per sequence of the last gradient call's last launch, the
+        number of checkpoint blocks in which the forward kernel took a power of two out of the state, and the blocks per
+        sequence."""
+        b, c = self.get_slab()
+        counts = np.zeros(max(b * c, 1), dtype=np.int64)
+        blocks = ctypes.c_int64()
+        _lib.check(_lib.load().phk_block_rescale_counts(self._h, counts.ctypes.data_as(ctypes.POINTER(ctypes.c_int64)),
+                                                        counts.size, ctypes.byref(blocks)))
+        return counts[: b * c], blocks.value
+
     def set_asm_run(self, on: bool):
         """The hand-written block-run sequence of the K = 16 float32 sweeps on / off (``phk_set_asm_run``; off = the C++ body)."""
         _lib.check(_lib.load().phk_set_asm_run(self._h, int(bool(on))))
