@@ -233,6 +233,49 @@ int phk_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pst
                const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* weights,
                int64_t wstride_b, const int64_t* lens, double* ll, void* tract, void* stream);
 
+/* Local likelihood-ratio scans (the reference has no counterpart): for every bin of scored sites of each sequence (b, s), the log
+ * of the ratio
+ *   P(o | the bin's sites are generated by an ALTERNATIVE model, the rest of the row by the fitted one) / P(o | fitted model),
+ * which says where along the row the fitted model is wrong and in which direction (an alternative with theta, rho or Ne scaled).
+ * phk_tracts is the special case "the same model with emissions multiplied by m"; an alternative with both emission rows set to 1
+ * gives the block-out predictive, logratio = -log P(o_bin | o_-bin).  Conventions of phk_posterior and phk_tracts: z_0 ~ pi
+ * precedes site 0, alpha_t is the forward vector after site t with alpha_{-1} = pi, beta_{L-1} = 1 and beta_t holds the emissions
+ * of sites t+1 .. L-1 only, a missing site has e = 1 in both models, the W warm-up sites are conditioned on and not reported, and
+ * there is no warm-up correction.  Let (A, e) be the particle's model and (A', e') its alternative block.  Bin k holds the scored
+ * sites s = W + k bin .. e = min(s + bin, L) - 1 (the last bin may be partial; nbin = ceil((L - W) / bin)), and
+ *   q_e        = beta_e
+ *   q_{t-1}    = A' (e'_{o_t} .* q_t)            for t = e, e-1, .., s
+ *   logratio_k = log sum_i alpha_{s-1}(i) q_{s-1}(i)  -  log sum_i alpha_{s-1}(i) beta_{s-1}(i):
+ * every site of the bin has the transition INTO it and its emission taken from the alternative; alpha, beta and the rest of the
+ * row are the fitted model's.
+ *   alt_params  the alternative blocks, laid out like params ([B, S|1, 7, K] in the handle's float type) with element strides
+ *               astride_b / astride_s (astride_s = 0: one block per particle; both 0: one block for all).  Their pi row is never
+ *               read: pi precedes site 0 and no bin contains it;
+ *   alt_prefold the pre-folded factors of the alternative blocks (phk_prefold), laid out like them with five rows, or NULL: as
+ *               prefold is to params.  The alternative folds its own hom emission into its own factors, by its own decision: a
+ *               block that cannot be folded runs unfolded;
+ *   logratio    [B, S, nbin] in the handle's float type, natural log;
+ *   ll          [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens        device int64 [N] or NULL: a site at or past its row's own length is stepped with the fitted model; a bin without
+ *               a site of the row's own is written as 0; an entry outside (W, L] is clamped and raises the bad-index flag.
+ * Unlike a tract, q is not bounded by beta and the ratio may leave the float range in either direction (with the emissions removed
+ * over a whole row it is 1 / P(o)).  q therefore carries an integer power-of-two exponent of its own relative to beta: it is
+ * renormalised where beta is rescaled, the exponent is folded into the ratio before the log while the product is representable
+ * and added in the log domain where it is not, so logratio is right wherever the true value is representable as a log.  An
+ * alternative block bit-identical to the fitted one gives exactly 0.  A bin whose denominator is not positive is written as 0 and
+ * raises the underflow flag (re-evaluate after phk_set_rescale_interval(h, 1)); a numerator of exactly 0 (an alternative that
+ * forbids the data) is a legitimate -inf and raises nothing.  With W = L there is no scored site: nbin = 0, ll = 0, logratio is
+ * empty and may be NULL.  params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs,
+ * slabs (phk_set_workspace_limit) and stream ordering are phk_posterior's, with the local-ratio sweep in the decode sweep's place
+ * (a hybrid plan runs as its serial half); the plan is read, never tuned or recorded.  Every bin is written once, by one unit:
+ * the same bits for any slab and any order of the units.  Stream-ordered; no two calls on one handle may overlap.  PHK_EINVAL,
+ * before anything is enqueued, for a NULL handle, NULL params / alt_params / inds / ll, bin < 1, W outside [0, L], NULL logratio
+ * with W < L. */
+int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const void* alt_params, int64_t astride_b, int64_t astride_s, const float* alt_prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens,
+                    double* ll, void* logratio, void* stream);
+
 /* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
  * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
  * precedes site 0, site t is step t + 1, a missing site has e = 1):

@@ -29,7 +29,8 @@ def __getattr__(name):
     if name == "posterior_tmrca":
         from .decode import posterior_tmrca
         return posterior_tmrca
-    if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check", "tract_posterior"):
+    if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check", "tract_posterior", "local_scan",
+                "LocalScan"):
         from . import decode
         return getattr(decode, name)
     if name == "RawContig":

@@ -24,6 +24,7 @@
 #include "trans_args.h"
 #include "loo_args.h"
 #include "tract_args.h"
+#include "local_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -37,7 +38,8 @@ namespace phk {
     hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);                \
     hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_loo_##tag(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st);     \
-    hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_local_##tag(int T, int nrm, const KArgs& a, const RArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -1014,9 +1016,9 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
                                             "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel",
                                             "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)",
                                             "loo_kernel (serial sweep)", "loo_kernel (segment sweep)", "tract_kernel (serial sweep)",
-                                            "tract_kernel (segment sweep)"};
+                                            "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 15 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 17 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1494,6 +1496,12 @@ struct TransOut {
     int64_t wstride_b;
     void* tract;  // ... into this output
     bool tracts;
+    // phk_local_ratio: the local-ratio sweep (launch_local.hip) runs instead, with these alternative blocks (laid out like params) ...
+    const void* alt;
+    int64_t astride_b, astride_s;
+    const float* alt_prefold;
+    void* logratio;  // ... into this output
+    bool local;
 };
 
 // Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
@@ -1501,7 +1509,8 @@ struct TransOut {
 // decoding leaves the autotune cache and everything a gradient call decides unchanged.
 // tr != nullptr (phk_transitions): the same legs, slabs and stream ordering with the transition sweep (launch_trans.hip) in the
 // decode sweep's place; values, mean and marginals are unused then.  tr->loo (phk_predictive): the leave-one-out predictive sweep
-// (launch_loo.hip) in that place.  tr->tracts (phk_tracts): the tract-posterior sweep (launch_tract.hip) in that place.
+// (launch_loo.hip) in that place.  tr->tracts (phk_tracts): the tract-posterior sweep (launch_tract.hip) in that place.  tr->local
+// (phk_local_ratio): the local likelihood-ratio sweep (launch_local.hip) in that place.
 static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                           const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                           double* ll, void* mean, void* marginals, void* stream, const TransOut* tr = nullptr) {
@@ -1513,7 +1522,12 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     if (tr && tr->tracts && !tr->weights) return fail(PHK_EINVAL, "weights must be a non-NULL device pointer (double [B, K] or [K])");
     if (tr && tr->tracts && tr->wstride_b < 0) return fail(PHK_EINVAL, "wstride_b must be >= 0");
     if (tr && tr->tracts && !tr->tract && W < h->L) return fail(PHK_EINVAL, "tract is NULL: nothing to compute");
-    if (tr && !tr->loo && !tr->tracts && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
+    if (tr && tr->local && !tr->alt) return fail(PHK_EINVAL, "alt_params must be a non-NULL device pointer (blocks laid out like params)");
+    if (tr && tr->local && (tr->astride_b < 0 || tr->astride_s < 0)) return fail(PHK_EINVAL, "astride_b and astride_s must be >= 0");
+    if (tr && tr->local && !tr->logratio && W < h->L) return fail(PHK_EINVAL, "logratio is NULL: nothing to compute");
+    if (tr && tr->local && tr->alt_prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+    if (tr && tr->local && tr->alt_prefold && (tr->astride_b % 7 != 0 || tr->astride_s % 7 != 0)) return fail(PHK_EINVAL, "alternative strides must be multiples of 7 (whole [7, K] blocks)");
+    if (tr && !tr->loo && !tr->tracts && !tr->local && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
     if (!tr && !mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
@@ -1547,9 +1561,16 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     case k: trc = h->dbl ? phk::launch_tract_f64_##k : phk::launch_tract_f32_##k; break;
     switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
 #undef PHK_CASE
+    typedef hipError_t (*lcl_fn)(int, int, const phk::KArgs&, const phk::RArgs&, int, int, hipStream_t);
+    lcl_fn lcl = nullptr;
+#define PHK_CASE(k) \
+    case k: lcl = h->dbl ? phk::launch_local_f64_##k : phk::launch_local_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
     const bool is_loo = tr && tr->loo;
     const bool is_trc = tr && tr->tracts;
-    const char* const sweep_name = is_trc ? "tract" : is_loo ? "predictive" : (tr ? "transition" : "decode");
+    const bool is_lcl = tr && tr->local;
+    const char* const sweep_name = is_lcl ? "local-ratio" : is_trc ? "tract" : is_loo ? "predictive" : (tr ? "transition" : "decode");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
@@ -1664,11 +1685,22 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             qa.weights = is_trc ? tr->weights + b0 * tr->wstride_b : nullptr;
             qa.wstride_b = is_trc ? tr->wstride_b : 0;
             qa.tract = is_trc && tr->tract ? (char*)tr->tract + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
+            phk::RArgs ra;
+            ra.bin = bin;
+            ra.nbin = nbin;
+            ra.lens = tr ? tr->lens : nullptr;
+            ra.alt = is_lcl ? (const char*)tr->alt + (size_t)(b0 * tr->astride_b + s0 * tr->astride_s) * rs : nullptr;
+            ra.astride_b = is_lcl ? tr->astride_b : 0;
+            ra.astride_s = is_lcl ? tr->astride_s : 0;
+            ra.apfstride_b = ra.astride_b / 7 * 5;  // laid out like the alternative blocks, five rows instead of seven
+            ra.apfstride_s = ra.astride_s / 7 * 5;
+            ra.alt_prefold = is_lcl && tr->alt_prefold ? tr->alt_prefold + (b0 * ra.apfstride_b + s0 * ra.apfstride_s) : nullptr;
+            ra.logratio = is_lcl && tr->logratio ? (char*)tr->logratio + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
             hipError_t e;
             if (!plan.segmented) {
                 e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-                e = is_trc ? trc(plan.T, h->nrm, a, qa, 0, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
+                e = is_lcl ? lcl(plan.T, h->nrm, a, ra, 0, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, 0, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", sweep_name, K, plan.T, hipGetErrorString(e));
                 continue;
             }
@@ -1681,7 +1713,7 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
             HIP_TRY(hipEventRecord(h->ev_join, h->side));
             HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            e = is_trc ? trc(plan.T, h->nrm, a, qa, units, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
+            e = is_lcl ? lcl(plan.T, h->nrm, a, ra, units, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, units, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
             if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", sweep_name, K, plan.T, units, hipGetErrorString(e));
         }
     }
@@ -1712,6 +1744,13 @@ int phk_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pst
                int64_t B, int64_t S, int64_t W, int bin, const double* weights, int64_t wstride_b, const int64_t* lens, double* ll,
                void* tract, void* stream) {
     const TransOut tr = {lens, nullptr, nullptr, nullptr, false, weights, wstride_b, tract, true};
+    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+}
+
+int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const void* alt_params, int64_t astride_b, int64_t astride_s, const float* alt_prefold, const int64_t* inds,
+                    int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* logratio, void* stream) {
+    const TransOut tr = {lens, nullptr, nullptr, nullptr, false, nullptr, 0, nullptr, false, alt_params, astride_b, astride_s, alt_prefold, logratio, true};
     return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
 }
 

@@ -6,11 +6,14 @@ The HMM posteriors come from the decode sweep of the HIP engine (``PSMCKernel.po
 from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sampling traceback (``PSMCKernel.sample_paths`` ->
 ``phk_sample_paths``), the breakpoint track from its transition sweep (``PSMCKernel.transitions`` -> ``phk_transitions``) and
 the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``) and the
-tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``); this module only builds the models, pads
-ragged inputs, averages, counts and run-length encodes.  There is no CPU path.
+tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``) and the local likelihood-ratio scans from its
+local-ratio sweep (``PSMCKernel.local_ratio`` -> ``phk_local_ratio``); this module only builds the models, pads ragged inputs,
+averages, counts and run-length encodes.  There is no CPU path.
 """
 
 from __future__ import annotations
+
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -18,7 +21,7 @@ import torch
 from .data import RawContig
 from .kernel import PSMCKernel
 from .params import PSMCParams
-from .size_history import DemographicModel
+from .size_history import DemographicModel, SizeHistory
 
 
 def _rows(data):
@@ -232,6 +235,93 @@ def tract_posterior(dms, data, t_max, t_min: float = 0.0, window_size: int = 100
     if spans is None:
         return track
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
+class LocalScan(NamedTuple):
+    """What ``local_scan`` returns: tensors on the device for a matrix, lists with one tensor per contig for a list."""
+
+    log_ratio: torch.Tensor  # float64 [N, nbin, J]: per row, bin and scale, the mean over the models of the per-model log ratios
+    composite: torch.Tensor  # float64 [nbin, J]: the sum of log_ratio over the rows (of the contig)
+    scales: tuple  # the J scales, ascending, 1.0 among them
+    best: torch.Tensor  # float64 [nbin]: the scale with the largest composite
+
+
+def local_scan(dms, data, what: str = "theta", scales=(0.25, 0.5, 2.0, 4.0), window_size: int = 100, bin: int = 100, device=None,
+               double_precision: bool = False):
+    """Where along the genome the fitted model is wrong, and in which direction: a per-bin profile likelihood over a scale of the
+    mutation rate, the recombination rate or the population size.  For every bin of ``bin`` windows and every scale s,
+    log P(data | the bin's windows generated by the model with ``what`` times s, the rest of the row by the model itself) -
+    log P(data | the model), exact (``PSMCKernel.local_ratio``, one sweep per scale): a window of doubled mutation rate, a
+    recombination cold spot, a region of reduced local Ne (background selection, a sweep).
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.  The log ratios
+        are averaged over the models with equal weight: that mean is the posterior expectation of the log likelihood ratio over
+        the ``fit()`` sample, NOT the log ratio of the mixture of the models (which would average the likelihoods before the log
+        is taken).
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, the padded windows belong to no alternative (each
+        row's own length goes to the kernel, which masks them) and are cut away again.
+    what: ``"theta"`` (the alternative has theta times s), ``"rho"`` (rho times s) or ``"ne"`` (``eta.c / s`` on the same time
+        grid: the population size times s).
+    scales: the scales to try; 1 is always part of the result, as the column of exact zeros, and costs no sweep.
+    Returns ``LocalScan(log_ratio, composite, scales, best)``: ``log_ratio`` float64 [N, nbin, J] with nbin = ceil(L / bin) and J
+    the number of scales (``scales``, ascending); ``composite`` [nbin, J], its sum over the rows: the scan of a cohort of pairs
+    treated as a composite likelihood, and the quantity to look at -- a single row's scan is confounded by the local TMRCA (a
+    deep local genealogy looks like a raised mutation rate), which differs from pair to pair while a property of the region does
+    not; ``best`` [nbin], the scale with the largest composite.  For a list of contigs the three are lists with one tensor per
+    contig (rows, bins and composite of that contig alone).
+    """
+    assert what in ("theta", "rho", "ne"), 'what: "theta", "rho" or "ne"'
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    sc = sorted({float(s) for s in scales} | {1.0})
+    assert all(np.isfinite(s) and s > 0 for s in sc), "scales must be positive and finite"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+
+    def blocks(models):  # [B, 1, M] fields: one block per model, broadcast over the rows
+        pps = [PSMCParams.from_dm(dm) for dm in models]
+        return PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                            for f in PSMCParams._fields))
+
+    def scaled(dm, s):
+        theta, rho, eta = float(dm.theta) * window_size, float(dm.rho) * window_size, dm.eta
+        if what == "theta":
+            theta *= s
+        elif what == "rho":
+            rho *= s
+        else:
+            eta = SizeHistory(t=eta.t, c=torch.as_tensor(eta.c, dtype=torch.float64) / s)
+        return DemographicModel(eta=eta, theta=theta, rho=rho)
+
+    pp = blocks([scaled(dm, 1.0) for dm in dms])
+    inds = torch.arange(rows.shape[0], device=dev)
+    N, nbin = rows.shape[0], (rows.shape[1] + bin - 1) // bin
+    lr = torch.zeros((N, nbin, len(sc)), dtype=torch.float64, device=dev)
+    for j, s in enumerate(sc):
+        if s == 1.0:
+            continue  # (the alternative is the model itself: exactly 0)
+        out = kern.local_ratio(pp, blocks([scaled(dm, s) for dm in dms]), inds, bin=bin, lens=lens)
+        lr[:, :, j] = out.log_ratio.to(torch.float64).mean(0)  # equal weight per model
+    sct = torch.tensor(sc, dtype=torch.float64, device=dev)
+    if spans is None:
+        comp = lr.sum(0)
+        return LocalScan(lr, comp, tuple(sc), sct[comp.argmax(-1)])
+    lrs = [lr[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+    comps = [x.sum(0) for x in lrs]
+    return LocalScan(lrs, comps, tuple(sc), [sct[c.argmax(-1)] for c in comps])
 
 
 def viterbi_tmrca(dm, data, window_size: int = 100, device=None, double_precision: bool = False):

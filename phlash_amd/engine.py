@@ -432,6 +432,63 @@ class HipEngine:
         _lib.check(rc)
         return ll, tract
 
+    def local_ratio(self, params: torch.Tensor, alt: torch.Tensor, inds: torch.Tensor, warmup: int = 0, bin: int = 1,
+                    lens: torch.Tensor | None = None):
+        """Local likelihood-ratio scan (``phk_local_ratio``): params / inds as ``run``.  ``alt``: the alternative blocks,
+        [B|1, S|1, 7, K] on the device (a leading 1 broadcasts over the particles, a second 1 over the chunks; the pi row is not
+        read).  Returns (ll [B, S] float64, logratio [B, S, nbin] in the handle's float type) over bins of ``bin`` scored sites
+        (nbin = ceil((L - warmup) / bin)): per bin log P(o | the bin's sites under the alternative, the rest under params) -
+        log P(o | params).  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
+        L``): a site at or past a row's own length is stepped with the fitted model, a bin without a site of the row's own is 0."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        assert alt.is_cuda and alt.device == self.device
+        assert alt.ndim == 4 and alt.shape[2] == 7 and alt.shape[3] == self.K_user, alt.shape
+        Ba, Sa = alt.shape[0], alt.shape[1]
+        assert Ba in (1, B) and Sa in (1, S), f"alt: [{B}|1, {S}|1, 7, K], got {tuple(alt.shape)}"
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+            pad = torch.zeros(alt.shape[:3] + (pad_k,), dtype=alt.dtype, device=alt.device)
+            pad[:, :, 4:6, :] = 1.0
+            alt = torch.cat([alt, pad], -1)
+        if lens is not None:
+            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
+            lens = lens.contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+
+        def blocks(x, nb, ns):  # -> (blocks in the handle's float type, pre-folded factors or None)
+            if x.dtype == torch.float64 and not self.double_precision and self.prefold:
+                x64 = x.contiguous()
+                p = torch.empty(x64.shape, dtype=torch.float32, device=self.device)
+                pf = torch.empty((nb, ns, 5, self.K), dtype=torch.float32, device=self.device)
+                _lib.check(_lib.load().phk_prefold(self.device.index, self.K, x64.data_ptr(), nb * ns, p.data_ptr(), pf.data_ptr(),
+                                                   None, ctypes.c_void_p(stream)))
+                return p, pf
+            return x.to(self.dtype).contiguous(), None
+
+        p, pf = blocks(params, B, Sp)
+        a, apf = blocks(alt, Ba, Sa)
+        inds = inds.contiguous()
+        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        out = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device)
+        rc = _lib.load().phk_local_ratio(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            a.data_ptr(), Sa * 7 * self.K if Ba == B and B > 1 else 0, 7 * self.K if Sa == S and S > 1 else 0,
+            apf.data_ptr() if apf is not None else None, inds.data_ptr(), B, S, int(warmup), int(bin),
+            lens.data_ptr() if lens is not None else None, ll.data_ptr(), out.data_ptr() if nbin > 0 else None,
+            ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        return ll, out
+
     def viterbi(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, lens: torch.Tensor | None = None):
         """Viterbi decoding (``phk_viterbi``): params / inds as ``run``.  Returns (logp [B, S] float64, path [B, S, L - warmup]
         uint8): the log probability of the single most probable hidden path of every sequence and its states at the sites

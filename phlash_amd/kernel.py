@@ -92,6 +92,16 @@ def _tracts_guarded(kern, *args, **kw):
     return out
 
 
+def _local_guarded(kern, *args, **kw):
+    """engine.local_ratio with the same safety net as ``_run_guarded`` (the local-ratio sweep raises the same underflow flag)."""
+    out = kern._eng.local_ratio(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.local_ratio(*args, **kw)
+    return out
+
+
 def _viterbi_guarded(kern, *args, **kw):
     """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
     out = kern._eng.viterbi(*args, **kw)
@@ -143,6 +153,13 @@ class Tracts(NamedTuple):
 
     ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
     prob: torch.Tensor  # [..., nbin]: E[prod of weights(z_t) over the bin's sites | o]
+
+
+class LocalRatio(NamedTuple):
+    """What ``PSMCKernel.local_ratio`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    log_ratio: torch.Tensor  # [..., nbin]: log P(o | the bin under the alternative) - log P(o)
 
 
 class Viterbi(NamedTuple):
@@ -417,6 +434,46 @@ class PSMCKernel:
                 assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
             ll, tract = _tracts_guarded(self, pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
         return Tracts(self._strip(ll, added_B, added_S), self._strip(tract, added_B, added_S))
+
+    # ---- local likelihood-ratio scans ------------------------------------------------------------
+    def local_ratio(self, pp, alt, index, *, bin: int = 1, lens=None) -> LocalRatio:
+        """Where the fitted model is wrong, and in which direction: for every bin of ``bin`` scored sites, ``log_ratio`` =
+        log P(o | the bin's sites generated by ``alt``, the rest of the row by ``pp``) - log P(o | ``pp``).  Every site of the bin
+        has the transition into it and its emission taken from ``alt``; the forward and backward vectors around the bin are those
+        of ``pp``, and ``alt``'s pi is never used.  The value is exact and is computed with an exponent of its own, so it is right
+        wherever it is representable as a log (the linear ratio need not be).  Special cases: an ``alt`` equal to ``pp`` with
+        both emission rows set to 1 gives the block-out predictive, ``log_ratio`` = -log P(o_bin | o_-bin) (at ``bin`` = 1 minus
+        the leave-one-out score ``predictive`` reports at the observed sites); an ``alt`` equal to ``pp`` with both emission rows
+        multiplied by an indicator of a set of states gives the log of ``tracts``' probability on rows without missing windows
+        (a missing window has emission 1 in both models, so there the indicator restricts nothing).  ``alt``: PSMCParams or
+        DemographicModel with the batch shapes of ``pp`` or broadcastable to them ([M]: one alternative for everything).
+        Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as ``loglik``); nbin =
+        ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <=
+        L``): a site at or past a row's own length is stepped with ``pp``, and a bin without a site of the row's own is 0.
+        Returns ``LocalRatio(ll, log_ratio)``, device tensors in ``float_type`` (ll float64); no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        if isinstance(alt, DemographicModel):
+            alt = PSMCParams.from_dm(alt)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            B, S, M = pa.shape[0], inds.shape[0], self.M
+            al = torch.stack([_as_tensor(a, self.device) for a in alt], -2)
+            assert al.shape[-2:] == (7, M) and 2 <= al.ndim <= 4, f"alt: fields [..., {M}], got {tuple(al.shape)}"
+            assert bool(torch.isfinite(al).all()), "not all parameters of alt finite"
+            if al.ndim == 2:  # one block for everything
+                al = al[None, None]
+            elif al.ndim == 3:  # one block per chunk, as pp
+                al = al[None]
+            assert al.shape[0] in (1, B) and al.shape[1] in (1, S), f"alt: batch shape of pp or broadcast to it, got {tuple(al.shape)}"
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            ll, lr = _local_guarded(self, pa, al, inds, warmup=self.overlap, bin=int(bin), lens=lens)
+        return LocalRatio(self._strip(ll, added_B, added_S), self._strip(lr, added_B, added_S))
 
     # ---- Viterbi decoding ---------------------------------------------------------------------
     def viterbi(self, pp, index, *, lens=None) -> Viterbi:
