@@ -331,6 +331,48 @@ int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64
                      const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, double* ll,
                      uint8_t* paths, int64_t path_stride, void* stream);
 
+/* Posterior predictive simulation (the reference has no counterpart): n_rep replicate observation rows of L sites drawn from
+ * the HMM of every (particle b, row s), laid under row s's accessibility mask; stored, or reduced on the fly to het counts
+ * per bin and a histogram of hom-run lengths, or both.  Device-level like phk_param_map: no handle, no plan, no upload.
+ * This comment is the definition; kernel and CPU restatement agree with it exactly, bit for bit.
+ *   params       device float64 [B, S or 1, 7, K], rows b,d,u,v,emis0,emis1,pi, element strides pstride_b / pstride_s
+ *                (pstride_s = 0: the particle's one block serves its S rows); K any integer in [2, 64], no padding.
+ *   arithmetic   IEEE float64, each operation rounded once, in the order written here; no division.
+ *   sequences    (b, s, r), r in [0, n_rep), numbered q = seq0 + b S + s: seq0 lets a caller cut a call into slabs over
+ *                particles without changing a draw.
+ *   uniforms     Philox4x32-10, key (seed mod 2^32, seed >> 32), multipliers, Weyl constants and the 53-bit formula
+ *                U(x, y) = (x 2^21 + (y >> 11)) 2^-53 of phk_sample_paths.  The block at counter (t, r, q mod 2^32, q >> 32)
+ *                serves site t: U1_t = U(x0, x1) drives the transition into site t, U2_t = U(x2, x3) the emission at site t;
+ *                the block at counter (0xFFFFFFFF, r, q lo, q hi) gives U0 = U(x0, x1) for the state before site 0.  Hence
+ *                L <= 2^32 - 2.
+ *   tables       per block, serial sums in ascending index: cp_j = sum_{k<=j} pi_k, cb_j = sum_{k<=j} b_k, cv_j = sum_{k<=j} v_k.
+ *   start        z = #{k <= K-2 : cp_k <= U0 cp_{K-1}}.
+ *   transition   from state i into site t: PB = cb_{i-1} (0 for i = 0), SV = cv_{K-1} - cv_i, tot = (PB + d_i) + u_i SV,
+ *                theta = U1_t tot.  theta < PB: j = #{k <= i-1 : cb_k <= theta}.  Otherwise phi = theta - PB; phi < d_i: j = i.
+ *                Otherwise psi = phi - d_i and j = min(K-1, i + 1 + #{k : i < k <= K-2, u_i (cv_k - cv_i) <= psi}).
+ *   emission     at state j the code is 1 (het) iff U2_t (emis0_j + emis1_j) < emis1_j, else 0 (the rows need not sum to one).
+ *   mask         device int8 [S, mask_stride] or NULL: where mask[s, t] < 0 the reported code is -1.  The hidden path and
+ *                every uniform are what they are without a mask; the mask is laid over the output only.
+ *   no mass      a draw whose total is not positive or not finite sets bit 0 of *flags (a plain store of 1) and is replaced:
+ *                cp_{K-1}: the start state is 0; tot of state i: the state stays i; emis0_j + emis1_j: the code is 0.  Each
+ *                of the three is judged alone, and the call completes normally.
+ * Outputs, each may be NULL (at least one is given):
+ *   obs          int8 [B, S, n_rep, row_stride]: the reported codes -1 / 0 / 1 at sites 0 .. L-1;
+ *   paths        uint8, same shape: the state at each site.  The kernel stores 16 bytes per lane: obs, paths (where given)
+ *                and row_stride must be multiples of 16 bytes, row_stride >= L.  Bytes at positions >= L of a row are
+ *                never written;
+ *   het          int32 [B, S, n_rep, nbin], nbin = ceil(L / bin): the sites of the bin whose reported code is 1;
+ *   runs         int32 [B, S, n_rep, 32]: histogram over floor(log2(len)) of the maximal runs of consecutive sites with
+ *                reported code 0; a het, a missing site or the end of the row ends a run, and a run is counted when it ends;
+ *   flags        one device int32, required; it is only ever set, the caller clears it.
+ * Stream-ordered, does not synchronise.  PHK_EINVAL, before anything is enqueued, for K outside [2, 64]; B, S, n_rep or
+ * L < 1; n_rep > 65535; L > 2^32 - 2; NULL params or flags; all four outputs NULL; bin < 1 with het given; with obs or
+ * paths given, row_stride < L or a violated alignment rule; mask_stride < L with a mask; more workgroups than one launch
+ * holds (2^31 - 1 of 64 sequences that share a parameter block). */
+int phk_simulate(int device, int K, const double* params, int64_t pstride_b, int64_t pstride_s, int64_t B, int64_t S,
+                 int64_t n_rep, int64_t L, uint64_t seed, int64_t seq0, const int8_t* mask, int64_t mask_stride, int8_t* obs,
+                 uint8_t* paths, int64_t row_stride, int bin, int32_t* het, int32_t* runs, int32_t* flags, void* stream);
+
 /* Particle -> PSMCParams for a whole population in one launch, float64, with its Jacobian.
  * Replaces, for B particles at once: MCMCParams.to_dm (src/phlash/params.py:94-127),
  * SizeHistory.ect / .pi (src/phlash/size_history.py:123-138,170-193), transition_matrix + _expQ

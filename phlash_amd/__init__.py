@@ -33,6 +33,9 @@ def __getattr__(name):
                 "LocalScan"):
         from . import decode
         return getattr(decode, name)
+    if name in ("simulate_rows", "replicate_check", "Simulated", "ReplicateCheck"):
+        from . import simulate
+        return getattr(simulate, name)
     if name == "RawContig":
         from .data import RawContig
         return RawContig

@@ -25,6 +25,7 @@
 #include "loo_args.h"
 #include "tract_args.h"
 #include "local_args.h"
+#include "simulate_args.h"
 
 namespace phk {
 #define PHK_DECL(tag)                                                                                                  \
@@ -1182,6 +1183,58 @@ int phk_param_map_rounded(int device, int K, int P, const int32_t* epoch_of_stat
     HIP_TRY(hipSetDevice(device));
     hipError_t e = phk::launch_param_map(a, (hipStream_t)stream);
     if (e != hipSuccess) return fail(PHK_EHIP, "param_map kernel launch: %s", hipGetErrorString(e));
+    return PHK_OK;
+}
+
+// Posterior predictive simulation (phk_simulate): one launch, no handle.
+int phk_simulate(int device, int K, const double* params, int64_t pstride_b, int64_t pstride_s, int64_t B, int64_t S, int64_t n_rep,
+                 int64_t L, uint64_t seed, int64_t seq0, const int8_t* mask, int64_t mask_stride, int8_t* obs, uint8_t* paths,
+                 int64_t row_stride, int bin, int32_t* het, int32_t* runs, int32_t* flags, void* stream) {
+    if (K < 2 || K > phk::SIM_MAXK) return fail(PHK_EINVAL, "K=%d outside [2, %d]", K, phk::SIM_MAXK);
+    if (B < 1 || S < 1 || n_rep < 1 || L < 1) return fail(PHK_EINVAL, "B, S, n_rep and L must be >= 1");
+    if (n_rep > 65535) return fail(PHK_EINVAL, "n_rep=%lld above 65535", (long long)n_rep);
+    if (L > 0xFFFFFFFELL) return fail(PHK_EINVAL, "L=%lld above 2^32 - 2", (long long)L);
+    if (!params || !flags) return fail(PHK_EINVAL, "NULL params or flags");
+    if (!obs && !paths && !het && !runs) return fail(PHK_EINVAL, "no output requested");
+    if (het && bin < 1) return fail(PHK_EINVAL, "bin must be >= 1");
+    if (obs || paths) {
+        if (row_stride < L) return fail(PHK_EINVAL, "row_stride=%lld below L=%lld", (long long)row_stride, (long long)L);
+        if (row_stride % 16 != 0 || (uintptr_t)obs % 16 != 0 || (uintptr_t)paths % 16 != 0)
+            return fail(PHK_EINVAL, "obs / paths and row_stride must be multiples of 16 bytes");
+    }
+    if (mask && mask_stride < L) return fail(PHK_EINVAL, "mask_stride=%lld below L=%lld", (long long)mask_stride, (long long)L);
+    if (B > 0x7FFFFFFFLL || S > 0x7FFFFFFFLL) return fail(PHK_EINVAL, "too many sequences for one launch: cut the call with seq0");
+    phk::SimArgs a;
+    a.K = K;
+    a.params = params;
+    a.pstride_b = pstride_b;
+    a.pstride_s = pstride_s;
+    a.B = B;
+    a.S = S;
+    a.n_rep = n_rep;
+    a.L = L;
+    a.key0 = (uint32_t)seed;
+    a.key1 = (uint32_t)(seed >> 32);
+    a.seq0 = seq0;
+    a.mask = mask;
+    a.mask_stride = mask_stride;
+    a.mask_vec = mask && (uintptr_t)mask % 16 == 0 && mask_stride % 16 == 0;
+    a.obs = obs;
+    a.paths = paths;
+    a.row_stride = row_stride;
+    a.bin = het ? bin : 1;
+    a.nbin = (L + a.bin - 1) / a.bin;
+    a.het = het;
+    a.runs = runs;
+    a.flags = flags;
+    a.per_row = pstride_s != 0 && S > 1;
+    a.per_block = a.per_row ? n_rep : S * n_rep;
+    a.chunks = (a.per_block + phk::SIM_NT - 1) / phk::SIM_NT;
+    a.nfull = L / phk::SIM_T;
+    if ((a.per_row ? B * S : B) > 0x7FFFFFFFLL / a.chunks) return fail(PHK_EINVAL, "too many sequences for one launch: cut the call with seq0");
+    HIP_TRY(hipSetDevice(device));
+    hipError_t e = phk::launch_simulate(a, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(PHK_EHIP, "simulate kernel launch: %s", hipGetErrorString(e));
     return PHK_OK;
 }
 
