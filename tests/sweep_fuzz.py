@@ -77,8 +77,8 @@ def _weights(rng, form, rows, K):
     return m
 
 
-def _draw(seed, kind, force_dbl):
-    d, rng = df._draw(seed, kind, force_dbl, with_rng=True)
+def lens_and_long_bin(d, rng):
+    """the sweep draws' long-bin rule and their three lens modes, drawn from ``rng`` after the posterior draw's fields"""
     if d.plan is not None and d.plan[0] == "segmented" and d.L - d.W > df.UNIT_SITES and d.n_units >= 2 and rng.integers(4) == 0:
         d.bin = int(rng.choice([513, 1000]))  # a bin longer than a unit, more often than the posterior draw has it
     mode = int(rng.integers(3))
@@ -90,6 +90,11 @@ def _draw(seed, kind, force_dbl):
             d.lens[d.inds[0]] = d.W + 1
             if d.S > 1 and d.inds[1] != d.inds[0]:
                 d.lens[d.inds[1]] = d.L
+
+
+def _draw(seed, kind, force_dbl):
+    d, rng = df._draw(seed, kind, force_dbl, with_rng=True)
+    lens_and_long_bin(d, rng)
     if kind == "transitions":
         d.arrivals = bool(rng.integers(3))
         flip = bool(rng.integers(2))
