@@ -501,12 +501,16 @@ int phk_set_loop_budget_scale(phk_handle* h, int kernels, int num, int den);
  * several states per lane rescale on demand at the default interval (a sequence only once its mass has fallen below 2^-16), so
  * nearly every block of an ordinary row counts 0 there; tests/test_rescale_on_demand.py reads how often the rescale fired. */
 int phk_block_rescale_counts(phk_handle* h, int64_t* counts, int64_t n, int64_t* blocks);
-/* Developer builds (-DPHK_ASM_RUN=1) only: the K = 16 float32 sweeps with two lanes per sequence run their hot blocks through a
- * hand-written instruction sequence (csrc/sweep_run_k16r2.inc, generated by scripts/gen_sweep_asm.py: the C++ body's arithmetic,
- * operation for operation, an all-hom block without its per-site tests) when on = 1.  It returns the same bits as the C++ body
- * (tests/test_hip_parity.py::test_asm_block_run_equals_the_cxx_body) and measured 1-2 % slower (profiles/r06_ab_experiments.txt
- * item 8), so the shipped library is built without it and answers on = 1 with PHK_EUNSUPPORTED. */
+/* The K = 16 float32 sweeps with two lanes per sequence run their hot blocks through a hand-written instruction sequence
+ * (csrc/sweep_run_k16r2.inc, generated by scripts/gen_sweep_asm.py: the C++ body's arithmetic, operation for operation, an all-hom
+ * block without its per-site tests and with the beta pass's suf(v.*w) kept for the forward pass).  It returns the same bits as the
+ * C++ body (tests/test_asm_run_default.py, tests/test_hip_parity.py::test_asm_block_run_equals_the_cxx_body).  A new K = 16
+ * float32 handle has it on; on = 0, or PHK_ASM_RUN=0 in the environment when the handle is created, selects the C++ body.  Handles
+ * of other kernels have no such sequence: the flag stays 0 whatever is asked.  A library built with -DPHK_ASM_RUN=0 answers
+ * on = 1 with PHK_EUNSUPPORTED.  Timings: profiles/ab_asm_run.txt. */
 int phk_set_asm_run(phk_handle* h, int on);
+/* 1 if the handle's sweeps use that sequence, else 0. */
+int phk_get_asm_run(const phk_handle* h);
 /* The same flag word handed over WITHOUT a host synchronisation: a one-thread kernel on `stream`
  * writes dst[0] = 1.0 if the underflow-risk bit is set (else 0.0), dst[1] = 1.0 if a chunk index was
  * outside [0, N) (else 0.0) -- `dst` is a device array of two doubles -- and clears the word.  The

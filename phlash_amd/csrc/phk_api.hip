@@ -173,7 +173,7 @@ struct phk_handle {
     int profiling = 0;
     double nonhom_frac = 0.0;  // share of the observation matrix that is het or missing (counted by pack_kernel)
     int mask_runs = 0;  // the rows hold runs of missing sites (pack_kernel: all-missing 8-site halves): KArgs::mask_runs
-    int asm_run = 0;  // phk_set_asm_run (developer builds with -DPHK_ASM_RUN=1)
+    int asm_run = 0;  // phk_set_asm_run; phk_create turns it on where the sequence exists (asm_run_kernels)
     int budget_num[3] = {1, 1, 1}, budget_den[3] = {1, 1, 1};  // phk_set_loop_budget_scale (tests): forward kernel, backward kernel, beta scan
     int poison = 0;  // diagnostic: fill the scratch buffers with this byte before every launch sequence (PHK_POISON=255: NaN patterns)
     std::vector<hipEvent_t> ev;  // triples (start, mid, end) per launch since the last timing query
@@ -208,6 +208,9 @@ bool pick_launchers(const phk_handle* h, Launchers* l) {
 #undef PHK_CASE
     return false;
 }
+
+// the handles whose sweeps have the hand-written block-run sequence (psmc_kernels.hip, PHK_ASM_RUN): K = 16, float32 kernels (R = 2 sweeps)
+bool asm_run_kernels(const phk_handle* h) { return h->K == 16 && !h->dbl; }
 
 bool valid_R(int K, int R) { return R >= 1 && R <= 16 && (R & (R - 1)) == 0 && R <= K && K % R == 0 && K / R <= 16; }
 // Variants that are not compiled (launch.hip mirrors these rules).  float64 kernels whose lanes own many
@@ -472,8 +475,10 @@ int enqueue(phk_handle* h, const Launchers& l, phk::KArgs a, const Plan& plan, b
     }
     h->eblk_nseq = nseq;  // what the forward kernel of this launch leaves in eblk: [blocks][nseq] (phk_block_rescale_counts)
     h->eblk_nblk = (h->L + plan.T - 1) / plan.T;
-    if (!h->dbl || plan.segmented) HIP_TRY(hipMemsetAsync(h->gacc.p, 0, (size_t)nseq * 6 * K * sizeof(double), st));
-    if (!plan.segmented && plan.hybrid_first > 0 && plan.hybrid_first < nseq && n_units(h, plan.T, a.W) >= 2) {
+    const bool hybrid = !plan.segmented && plan.hybrid_first > 0 && plan.hybrid_first < nseq && n_units(h, plan.T, a.W) >= 2;
+    // (float64 too where a segment sweep runs: its unit 0 adds into the buffer)
+    if (!h->dbl || plan.segmented || hybrid) HIP_TRY(hipMemsetAsync(h->gacc.p, 0, (size_t)nseq * 6 * K * sizeof(double), st));
+    if (hybrid) {
         // hybrid: forward kernel over everything || beta scan over the tail range; then the serial
         // sweep of the head range || the segment sweep + finalize of the tail range
         phk::KArgs a1 = a, a2 = a;
@@ -486,7 +491,6 @@ int enqueue(phk_handle* h, const Launchers& l, phk::KArgs a, const Plan& plan, b
         const int units = (int)n_units(h, plan.T, a.W);
         if (int rc = ensure_part(h, nseq - plan.hybrid_first, units); rc != PHK_OK) return rc;
         a2.part = h->part.p;
-        HIP_TRY(hipMemsetAsync(h->gacc.p, 0, (size_t)nseq * 6 * K * sizeof(double), st));  // (float64 too: unit 0 of a segment sweep adds into it)
         HIP_TRY(hipEventRecord(h->ev_fork, st));
         HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
         // (forward kernel first: its 784 lone waves are to be on their SIMDs before the scan's 4,376 fill the slots)
@@ -814,7 +818,8 @@ int phk_create(phk_handle** out, int K, const int8_t* data, int64_t N, int64_t L
     if (const char* env = std::getenv("PHK_DETERMINISTIC")) h->deterministic = std::atoi(env) != 0;
     if (const char* env = std::getenv("PHK_POISON")) h->poison = std::atoi(env);
 #if PHK_ASM_RUN
-    if (const char* env = std::getenv("PHK_ASM_RUN")) h->asm_run = std::atoi(env) != 0;
+    h->asm_run = asm_run_kernels(h) ? 1 : 0;
+    if (const char* env = std::getenv("PHK_ASM_RUN")) h->asm_run = (std::atoi(env) != 0 && asm_run_kernels(h)) ? 1 : 0;
 #endif
     if (h->risk.ensure(4 * sizeof(int)) != PHK_OK || hipMemset(h->risk.p, 0, 4 * sizeof(int)) != hipSuccess) {  // flag word + (kernel, sequence, block) of an overrun
         delete h;
@@ -1036,11 +1041,13 @@ int phk_take_flags_async(phk_handle* h, double* dst, void* stream) {
 int phk_set_asm_run(phk_handle* h, int on) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
 #if !PHK_ASM_RUN
-    if (on) return fail(PHK_EUNSUPPORTED, "this library was built without the hand-written block-run sequence (-DPHK_ASM_RUN=1: developer builds)");
+    if (on) return fail(PHK_EUNSUPPORTED, "this library was built without the hand-written block-run sequence (-DPHK_ASM_RUN=0)");
 #endif
-    h->asm_run = on ? 1 : 0;
+    h->asm_run = (on && asm_run_kernels(h)) ? 1 : 0;  // (other kernels have no such sequence: the flag stays off)
     return PHK_OK;
 }
+
+int phk_get_asm_run(const phk_handle* h) { return h ? h->asm_run : 0; }
 
 int phk_set_loop_budget_scale(phk_handle* h, int kernels, int num, int den) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");

@@ -291,10 +291,10 @@ constexpr float RATIO_MIN_EMIS0 = 0x1p-64f;
 #define PHK_FOLD 1  // A/B: 0 = no float32 kernel folds its hom emission into the factors
 #endif
 #ifndef PHK_ASM_RUN
-#define PHK_ASM_RUN 0  // 1 (developer builds: make -C phlash_amd/csrc OUT=exp/libphk_asm.so OBJDIR=/tmp/build_asm EXTRA=-DPHK_ASM_RUN=1, run with PHK_LIB): the K = 16, R = 2 float32 sweeps run their
-                       // hot blocks through the generated instruction sequence sweep_run_k16r2.inc (scripts/gen_sweep_asm.py) when the
-                       // handle asks for it (phk_set_asm_run).  Bit-identical to the C++ body and 1-2 % SLOWER than it
-                       // (profiles/r06_ab_experiments.txt item 8), hence not in the shipped library
+#define PHK_ASM_RUN 1  // 1: the K = 16, R = 2 float32 sweeps run their hot blocks through the generated instruction sequence
+                       // sweep_run_k16r2.inc (scripts/gen_sweep_asm.py) unless the handle asks for the C++ body (phk_set_asm_run(h, 0),
+                       // PHK_ASM_RUN=0 in the environment).  Bit-identical to the C++ body (tests/test_asm_run_default.py); 0 builds a
+                       // library without the sequence (EXTRA=-DPHK_ASM_RUN=0).  Timings: profiles/ab_asm_run.txt
 #endif
 #ifndef PHK_FOLD_F64
 #define PHK_FOLD_F64 1  // A/B: 0 = the float64 kernels keep their emissions in the table (rounds 1-5); 1: folded like the float32 ones (round 6: cfg2 76 -> 67 ms)
@@ -1714,6 +1714,9 @@ __global__ __launch_bounds__(NT_MAX, (bwd_waves_per_simd<real, K, R, T, SEG>()))
             // register plan -- what the compiler cannot do at the join of two C++ bodies.  Same arithmetic, operation for
             // operation; waves that hold more than two observation rows keep the C++ loop.
             if constexpr (HREG && !HREG2 && sizeof(real) == 4 && K == 16 && R == 2) {
+                // (an all-hom block of the sequence parks two w vectors where the loop below parks its own: the offsets are the generator's)
+                static_assert(L::ETAB_STRIDE == 28 && L::EROW == 8 && PARKN == 2 && sweep_lds_stride<real, K, R, T, NRM>() == 68,
+                              "sweep_run_k16r2.inc: the thread's LDS slice is table 28 + mass rows 24 + parked 16 floats");
                 if (A.asm_run != 0 && two_rows && blk >= stop) {
                     // (the statement's scalar operands must be SGPRs to the compiler's divergence analysis, which cannot see that
                     // `stop` -- it depends on whether this unit owns a partial-sum slot -- is the same in every lane)

@@ -122,6 +122,10 @@ class HipEngine:
         """The hand-written block-run sequence of the K = 16 float32 sweeps on / off (``phk_set_asm_run``; off = the C++ body)."""
         _lib.check(_lib.load().phk_set_asm_run(self._h, int(bool(on))))
 
+    def get_asm_run(self) -> bool:
+        """Whether the sweeps of this handle use that sequence: the default for K = 16 float32 (``phk_get_asm_run``)."""
+        return bool(_lib.load().phk_get_asm_run(self._h))
+
     def set_deterministic(self, on: bool):
         _lib.check(_lib.load().phk_set_deterministic(self._h, int(bool(on))))
 

@@ -10,19 +10,27 @@ hot blocks: the loop, the prefetch of checkpoints / block exponents / observatio
 without tests and a mixed body with them, under ONE register plan, as one asm statement whose operands are the run's state.
 
 The arithmetic is the C++ body's, operation for operation (psmc_kernels.hip, bwd_kernel, PHK_HET_REGS body; Lane::scans,
-scans_adj, suffix_vw, beta_prev, carry with the SPLIT layout at R = 2): every fma / mul / add of the C++ source is one
-instruction here with the same operands in the same order, so the results are bit-identical
-(tests/test_hip_parity.py::test_asm_block_run_equals_the_cxx_body).
+scans_adj, suffix_vw, beta_prev, carry with the SPLIT layout at R = 2): every fma / mul / add whose result the C++ source
+uses is one instruction here with the same operands in the same order, so the results are bit-identical
+(tests/test_asm_run_default.py, tests/test_hip_parity.py::test_asm_block_run_equals_the_cxx_body).  What is NOT repeated is
+suf(v.*w) of a site where the forward pass can still find the beta pass's copy in registers (the same instructions on the same
+inputs: the same bits): six of the eight sites of an all-hom block, three of a mixed one (see SAVED_HOM / SAVED_MIXED in build()).
+
+    python scripts/gen_sweep_asm.py [out.inc]     write the sequence (the Makefile's rule) and print the counts below
+    python scripts/gen_sweep_asm.py --report      only print, per kind of block, the instructions of one trip through the loop
 
 Register plan (physical VGPRs are clobbers of the statement; the state's registers are its operands, chosen by the compiler):
     v[TBASE ...]   R[j][h], j = 0..7: the block's w vectors / the beta chain (w_j lives in R[j+1], the incoming beta -- an
-                   operand -- is R[8]);  forward-pass temporaries: A / T (state, ping-pong), the three scan chains X (prefix of
+                   operand -- is R[8]; beta travels from block to block in R[0]);  forward-pass temporaries: A (the checkpoint
+                   state; later states live in the Z chain and in consumed w vectors), the three scan chains X (prefix of
                    u.*a), Y (suffix of a), Z (suffix of v.*w), lane totals, carries;  the prefetched checkpoint (two quads),
-                   codes, scale, addresses.
-Hazards are kept by construction: `emit()` records the registers every instruction defines and uses, and `finish()` inserts an
-s_nop wherever (a) a packed-float32 instruction's result would be read by the very next instruction, or a packed instruction
+                   codes, scale, addresses;  and the registers that keep a site's suf(v.*w) from one pass to the other.
+Hazards are kept by construction: `emit()` records the registers every instruction defines and uses, and `finish()` looks for
+the places where (a) a packed-float32 instruction's result would be read by the very next instruction, or a packed instruction
 would read a result of the very next-to-last one (one wait state, r05 item 19), (b) a DPP or readlane operand was written less
-than three instructions earlier (two wait states).
+than three instructions earlier (two wait states).  There it first tries to pull up a later instruction of the same straight-line
+stretch that depends on nothing it passes (`hoist()`: plain vector arithmetic only) and inserts an s_nop only if there is none;
+as generated, neither kind of block has one left.
 """
 import sys
 
@@ -142,27 +150,63 @@ class Gen:
         self.emit(f"v_mov_b64_e32 {self.txt(d)}, {self.txt(s)}", [d], [s])
 
     # ---- finishing: hazards ----------------------------------------------------------------------------------------------
+    @staticmethod
+    def gap_needed(hist, u, kind):
+        """wait states an instruction of `kind` that reads `u` needs after the instructions of `hist` (most recent last)"""
+        need = 0
+        if kind in ("valu", "pk", "dpp", "lane", "vmem_addr", "lds"):
+            for back, (pd, pk) in enumerate(reversed(hist[-3:])):  # back = 0: previous instruction
+                if not (pd & u):
+                    continue
+                if kind in ("dpp", "lane"):
+                    need = max(need, 2 - back)
+                elif pk == "pk" or kind == "pk":
+                    need = max(need, 1 - back)
+        return need
+
+    HOIST_WINDOW = 24  # how far ahead finish() looks for an instruction to put where an s_nop would go
+
+    def hoist(self, k, hist):
+        """Index of a later instruction that may run where instruction k would need a wait state, or None.  Only plain vector
+        arithmetic moves, and only over plain vector arithmetic (every register these read or write is on record; nothing that
+        touches vcc, exec, memory or a scalar register is moved or crossed), and only if it depends on nothing it passes --
+        no register of its own is read or written there, none it reads is written there: the values are the same, bit for bit --
+        and needs no wait state itself."""
+        for j in range(k + 1, min(k + 1 + self.HOIST_WINDOW, len(self.ins))):
+            passed = self.ins[j - 1]
+            if passed[3] not in ("valu", "pk", "dpp") or "vcc" in passed[0]:
+                return None
+            text, d, u, kind = self.ins[j]
+            if kind not in ("valu", "pk") or "vcc" in text:
+                continue
+            if any((d & (pd | pu)) or (u & pd) for _, pd, pu, _ in self.ins[k:j]):
+                continue
+            if self.gap_needed(hist, u, kind) > 0:
+                continue
+            return j
+        return None
+
     def finish(self):
         out = []   # final instruction list
         hist = []  # (defs, kind) of the last real instructions, most recent last ("nop" entries have empty defs)
         nops = 0
-        for text, d, u, kind in self.ins:
+        k = 0
+        while k < len(self.ins):
+            text, d, u, kind = self.ins[k]
             if kind == "label":
                 out.append(text)
                 hist = []  # a join: be conservative, treat as fresh (the predecessor's last instructions are unknown)
                 # conservative: after a label require the generic gaps again by assuming a packed write of everything -> handled by
                 # emitting an s_nop 1 at labels that are branch targets (cheap: labels are block / run boundaries or cold paths)
+                k += 1
                 continue
-            need = 0
-            if kind in ("valu", "pk", "dpp", "lane", "vmem_addr", "lds"):
-                for back, (pd, pk) in enumerate(reversed(hist[-3:])):  # back = 0: previous instruction
-                    if not (pd & u):
-                        continue
-                    gap_have = back
-                    if kind in ("dpp", "lane"):
-                        need = max(need, 2 - gap_have)
-                    elif pk == "pk" or kind == "pk":
-                        need = max(need, 1 - gap_have)
+            need = self.gap_needed(hist, u, kind)
+            if need > 0:
+                j = self.hoist(k, hist)
+                if j is not None:  # an independent instruction of the same straight-line stretch takes the wait state's place
+                    self.ins.insert(k, self.ins.pop(j))
+                    continue
+            k += 1
             if need > 0:
                 out.append(f"s_nop {need - 1}")
                 nops += 1
@@ -198,7 +242,9 @@ def build():
     CKSTEP, EBSTEP, CKPIECE = "%[ckstep]", "%[ebstep]", "%[ckpiece]"  # 64-bit SGPR pairs: -ck_step bytes, -eb step bytes, +piece distance bytes
 
     # ---- temporaries ----------------------------------------------------------------------------------------------------
+    CKQ2 = g.pair()                                           # (first: everything below then starts on a multiple of four)
     R = [[g.pair() for h in range(NP)] for j in range(T)]   # R[j]: beta after site j's step = w of site j - 1 ... (see below)
+    assert R[0][0][1] % 4 == 0                                # (an R[j] is two quads: parked by two 16-byte LDS accesses)
     A = [g.pair() for h in range(NP)]
     Tt = [g.pair() for h in range(NP)]
     # the scan chains as quads (so that the cold missing-site bodies can land their 16-byte LDS rows in them: the chains are dead there)
@@ -209,18 +255,20 @@ def build():
     LTX, LTY, LTZ = g.pair(), g.pair(), g.pair()
     CX, CY, CZ = g.pair(), g.pair(), g.pair()
     PQ0, PQ1 = g.quad(), g.quad()                            # checkpoint pieces: states 0..3 / 4..7 of the lane
-    CKQ2 = g.pair()
     ADDR = g.pair()
     FXP = g.pair()                                            # the block's scale 2^-e in the low half (read as a pair by v_pk_mul)
     FX = g.lo(FXP)
-    CODES, TMP, C16, CC, LADDR = g.single(), g.single(), g.single(), g.single(), g.single()
+    # the scalars of enter() and of the cold bodies, as halves of pairs: an all-hom block has no use for them once it is entered, and
+    # its body keeps a site's suf(v.*w) in the four pairs (SAVED sets, below)
+    TAIL = [g.pair() for _ in range(4)]
+    CODES, TMP, CC, LADDR = g.lo(TAIL[0]), g.hi(TAIL[0]), g.lo(TAIL[1]), g.hi(TAIL[1])
     ER0, ER1, GR0, GR1 = XQ[0], XQ[1], YQ[0], YQ[1]            # missing-site path: emission row and mass row halves (dead chains)
     S_T0, S_W, S_SH, S_A, S_B, S_U, S_NH, S_NM, S_TMP = "s88", "s89", "s90", "s91", "s92", "s93", "s94", "s95", "s96"
     S_SAVE = "s[98:99]"
     S_OFF = "s[86:87]"
 
     W = lambda i: (B if i == T - 1 else R[i + 1])  # w of site i lives where beta stood when the site was entered
-    # beta after site i's step goes to R[i]; block output R[0] -> copied to B at the block's end
+    # beta after site i's step goes to R[i]; the block's output R[0] is the next block's input (scaled into B at its top)
 
     def quad_lane(q, i):
         return ("s", q[1] + i)
@@ -230,6 +278,10 @@ def build():
         g.emit(f"v_mov_b32_e32 {g.txt(quad_lane(PQ0, i))}, {AN[i]}", [quad_lane(PQ0, i)], [AN[i]])
         g.emit(f"v_mov_b32_e32 {g.txt(quad_lane(PQ1, i))}, {AN[4 + i]}", [quad_lane(PQ1, i)], [AN[4 + i]])
     g.emit(f"v_lshl_add_u64 {g.txt(CKQ2)}, {CKQ}, 0, {CKPIECE}", [CKQ2], [CKQ], "valu")
+    # beta travels from block to block in R[0], where the beta pass leaves it: the scale at a block's top moves it to B (= w of the
+    # block's last site) on the way, and only the run's two ends copy
+    for h in range(NP):
+        g.mov64(R[0][h], B[h])
 
     top = g.newlabel("top")
     g.label(top)
@@ -250,11 +302,11 @@ def build():
     g.emit("s_nop 0", kind="salu")
     g.emit(f"global_load_dword {WPREV}, {g.txt(ADDR)}, off", [WPREV], [ADDR], "vmem")
     g.label(same)
-    g.emit("s_nop 1", kind="salu")
-    # codes = wcur >> (2 * (t0 & 15)); t0 & 15 is 0 or 8
+    # codes = the block's sixteen bits of wcur, from bit 2 * (t0 & 15) on; t0 & 15 is 0 or 8.  (Read by the masks far below: the
+    # two lane reads there then need no wait state.  wcur, if just stepped, was written three instructions back by a plain move.)
     g.emit(f"s_and_b32 {S_SH}, {S_T0}, 8", kind="salu")
     g.emit(f"s_lshl_b32 {S_SH}, {S_SH}, 1", kind="salu")
-    g.emit(f"v_lshrrev_b32_e32 {g.txt(CODES)}, {S_SH}, {WCUR}", [CODES], [WCUR])
+    g.emit(f"v_bfe_u32 {g.txt(CODES)}, {WCUR}, {S_SH}, 16", [CODES], [WCUR])
     # al0: state i of the lane -> pair i % 4, half i / 4
     for h in range(NP):
         g.emit(f"v_mov_b32_e32 {g.txt(g.lo(A[h]))}, {g.txt(quad_lane(PQ0, h))}", [g.lo(A[h])], [quad_lane(PQ0, h)])
@@ -273,19 +325,15 @@ def build():
     g.emit(f"v_lshl_add_u64 {g.txt(CKQ2)}, {g.txt(CKQ2)}, 0, {CKSTEP}", [CKQ2], [CKQ2])
     g.emit(f"v_lshl_add_u64 {EBQ}, {EBQ}, 0, {EBSTEP}", [EBQ], [EBQ])
     g.label(nopf)
-    g.emit("s_nop 1", kind="salu")
-    # scale: beta[h] *= fx (both halves from the one register: op_sel_hi[0] = 0)
+    # scale: beta = fx * (beta as the last block left it), both halves from the one register: op_sel_hi[0] = 0.  (Nothing the
+    # prefetch writes is read here, and fx is at least two instructions old on either path: no wait state.)
     for h in range(NP):
-        g.emit(f"v_pk_mul_f32 {B[h]}, {g.txt(FXP)}, {B[h]} op_sel_hi:[0,1]", [B[h]], [FX, B[h]], "pk")
+        g.emit(f"v_pk_mul_f32 {B[h]}, {g.txt(FXP)}, {g.txt(R[0][h])} op_sel_hi:[0,1]", [B[h]], [FX, R[0][h]], "pk")
     # masks: OR over the wave of the block's code bits = lane 0's | lane 63's (the wave holds at most two rows)
-    g.emit(f"v_and_b32_e32 {g.txt(C16)}, 0xffff, {g.txt(CODES)}", [C16], [CODES])
-    g.emit("s_nop 1", kind="salu")
-    g.emit(f"v_readfirstlane_b32 {S_A}, {g.txt(C16)}", [], [C16], "lane")
-    g.emit(f"v_readlane_b32 {S_B}, {g.txt(C16)}, 63", [], [C16], "lane")
-    g.emit("s_nop 0", kind="salu")
+    g.emit(f"v_readfirstlane_b32 {S_A}, {g.txt(CODES)}", [], [CODES], "lane")
+    g.emit(f"v_readlane_b32 {S_B}, {g.txt(CODES)}, 63", [], [CODES], "lane")
     g.emit(f"s_or_b32 {S_U}, {S_A}, {S_B}", kind="salu")
     g.emit(f"s_lshr_b32 {S_TMP}, {S_U}, 1", kind="salu")
-    g.emit(f"s_and_b32 {S_NM}, {S_TMP}, 0x5555", kind="salu")
     g.emit(f"s_or_b32 {S_NH}, {S_U}, {S_TMP}", kind="salu")
     g.emit(f"s_and_b32 {S_NH}, {S_NH}, 0x5555", kind="salu")
     g.emit(f"s_cmp_eq_u32 {S_NH}, 0", kind="salu")
@@ -295,16 +343,49 @@ def build():
 
     cold = []  # out-of-line bodies of the mixed path: (label, emitter function)
 
-    def beta_site(i, tests):
+    # ---- suf(v.*w) of a site, kept from the beta pass for the forward pass ------------------------------------------------
+    # The beta pass computes suf(v.*w_i) for the beta recursion, the forward pass needs the same vector again for gu: a site
+    # whose vector survives in registers saves the forward pass its eleven instructions (four fmas, the lane total, the carry,
+    # four adds).  Registers for that, per block kind (the plan at a block's entry and exit is the same for both):
+    #   site 0       its vector is the last one the beta pass computes: it simply stays in the Z chain;
+    #   SAVED sets   Tt (the state lives in the Z chain and in consumed w vectors during the forward pass, below);  the address /
+    #                scale pairs of enter() with the Z chain's own total and carry (the beta pass borrows the Y chain's, idle
+    #                there);  and, in an all-hom block only, the scalars of enter() and of the cold bodies (TAIL).
+    # The state of the forward pass: a_0 = A (the checkpoint);  p of site 0 goes to the Z chain (site 0's vector has been used by
+    # then, and the Z chain is computed again only from the first site without a saved vector on);  p of site i >= 1 goes to
+    # R[i] = w of site i - 1, consumed one site earlier.
+    #   PARKED       an all-hom block parks w of sites 5 and 6 (R[6], R[7]: written first by the beta pass, read last by the forward
+    #                pass) in the thread's LDS slice, in the sixteen floats where the C++ body parks its two vectors, as soon as
+    #                the beta pass has read them; their registers then keep the vectors of sites 4 and 5.  The forward pass
+    #                asks for a parked w one site ahead, right after the kept vector in its registers has been used.
+    SAVED_HOM = {1: Tt, 2: [ADDR, FXP, LTZ, CZ], 3: TAIL, 4: R[6], 5: R[7]}
+    SAVED_MIXED = {1: Tt, 2: [ADDR, FXP, LTZ, CZ]}
+    PARK_BYTE = (28 + 24) * 4  # the slice: emission table (Lane::ETAB_STRIDE = 28 floats), three mass rows, the parked vectors
+    PARKED = {6: PARK_BYTE, 7: PARK_BYTE + 32}  # R[j] -> byte offset in the slice (sweep_lds_stride: 68 floats = 272 bytes)
+
+    def park(j, store):
+        for q in range(2):
+            quad = ("q", R[j][2 * q][1])
+            off = PARKED[j] + 16 * q
+            assert off + 16 <= 68 * 4
+            if store:
+                g.emit(f"ds_write_b128 {LDS}, {g.txt(quad)} offset:{off}", [], [LDS, quad], "lds")
+            else:
+                g.emit(f"ds_read_b128 {g.txt(quad)}, {LDS} offset:{off}", [quad], [LDS], "lds")
+
+    def beta_site(i, tests, ZC):
+        """ZC: the four pairs of the site's Z chain (the chain's own registers, or a SAVED set)"""
+        LTZ, CZ = LTY, CY
         Wi = W(i)
         Bn = R[i]
         if tests:
             lab = g.newlabel(f"bh{i}")
             ret = g.newlabel(f"br{i}")
+            # (no wait state behind the label: what reads w next is packed, not DPP, and is two instructions -- the test -- behind w's
+            # last write on the fall-through and one -- the branch back -- behind the cold body's)
             g.emit(f"s_bitcmp1_b32 {S_NH}, {2 * i}", kind="salu")
             g.emit(f"s_cbranch_scc1 {lab}", kind="branch")
             g.label(ret)
-            g.emit("s_nop 0", kind="salu")
             cold.append(("beta", i, lab, ret))
         # suffix of v.*w (Z chain) and prefix of b.*w (X chain), interleaved
         g.pk_fma(ZC[0], Pv[3], Wi[3], None)
@@ -336,48 +417,78 @@ def build():
         for h in range(NP):
             g.pk_fma(Bn[h], Pu[h], svw[h], YC[h])
 
-    def fwd_site(i, tests, a, t):
-        """a: registers of the state entering the site; t: where p = A' a goes (the next site's a)"""
+    def fwd_site(i, tests, a, t, kept, refill=None, wait=False):
+        """a: registers of the state entering the site; t: where p = A' a goes (the next site's a); kept: the four pairs that hold
+        the site's Z chain from the beta pass (None: it is computed here, in the Z chain's own registers); refill: the R[j] to
+        read back from LDS once `kept` has been used; wait: this site's w was asked for by the site before"""
         Wi = W(i)
         last = i == T - 1
-        g.pk_fma(XC[0], Pu[0], a[0], None)
-        g.pk_add(YC[0], a[3], None)            # 0 + a3
-        g.pk_fma(ZC[0], Pv[3], Wi[3], None)
-        g.pk_fma(XC[1], Pu[1], a[1], XC[0])
-        g.pk_add(YC[1], YC[0], a[2])
-        g.pk_fma(ZC[1], Pv[2], Wi[2], ZC[0])
-        g.pk_fma(XC[2], Pu[2], a[2], XC[1])
-        g.pk_add(YC[2], YC[1], a[1])
-        g.pk_fma(ZC[2], Pv[1], Wi[1], ZC[1])
-        g.pk_fma(XC[3], Pu[3], a[3], XC[2])    # tu
-        g.pk_add(YC[3], YC[2], a[0])           # ta
-        g.pk_fma(ZC[3], Pv[0], Wi[0], ZC[2])   # tv
-        g.lane_total(LTX, XC[3])
-        g.lane_total(LTY, YC[3])
-        g.lane_total(LTZ, ZC[3])
+        if wait and kept is None:  # (the Z chain reads w at once)
+            g.emit("s_waitcnt lgkmcnt(0)", kind="wait")
+        if kept is not None:
+            # the chains of u.*a and a alone; the site's gu and gd rows need no scan of this pass and fill the chains' gaps
+            svw = [kept[2], kept[1], kept[0], kept[3]]
+            g.pk_fma(XC[0], Pu[0], a[0], None)
+            g.pk_add(YC[0], a[3], None)            # 0 + a3
+            g.pk_fma(GU[0], a[0], svw[0], GU[0])
+            g.pk_fma(XC[1], Pu[1], a[1], XC[0])
+            g.pk_add(YC[1], YC[0], a[2])
+            g.pk_fma(GU[1], a[1], svw[1], GU[1])
+            g.pk_fma(XC[2], Pu[2], a[2], XC[1])
+            g.pk_add(YC[2], YC[1], a[1])
+            g.pk_fma(GU[2], a[2], svw[2], GU[2])
+            g.pk_fma(XC[3], Pu[3], a[3], XC[2])    # tu
+            g.pk_add(YC[3], YC[2], a[0])           # ta
+            g.pk_fma(GU[3], a[3], svw[3], GU[3])
+            g.lane_total(LTX, XC[3])
+            g.lane_total(LTY, YC[3])
+            if wait:  # (nothing above reads w: the wait stands behind fourteen instructions of this site and before the next request)
+                g.emit("s_waitcnt lgkmcnt(0)", kind="wait")
+            if refill is not None:  # the kept vector has been used: its registers take back the parked w the next site reads
+                park(refill, store=False)
+        else:
+            g.pk_fma(XC[0], Pu[0], a[0], None)
+            g.pk_add(YC[0], a[3], None)            # 0 + a3
+            g.pk_fma(ZC[0], Pv[3], Wi[3], None)
+            g.pk_fma(XC[1], Pu[1], a[1], XC[0])
+            g.pk_add(YC[1], YC[0], a[2])
+            g.pk_fma(ZC[1], Pv[2], Wi[2], ZC[0])
+            g.pk_fma(XC[2], Pu[2], a[2], XC[1])
+            g.pk_add(YC[2], YC[1], a[1])
+            g.pk_fma(ZC[2], Pv[1], Wi[1], ZC[1])
+            g.pk_fma(XC[3], Pu[3], a[3], XC[2])    # tu
+            g.pk_add(YC[3], YC[2], a[0])           # ta
+            g.pk_fma(ZC[3], Pv[0], Wi[0], ZC[2])   # tv
+            g.lane_total(LTX, XC[3])
+            g.lane_total(LTY, YC[3])
+            g.lane_total(LTZ, ZC[3])
         # gd += w .* a (needs nothing of the scans: fills the gap before the DPP reads)
         for h in range(NP):
             g.pk_fma(GD[h], Wi[h], a[h], GD[h])
         g.carry(CX, LTX, XC[3], UP1, prefix=True)     # cu
         g.carry(CY, LTY, YC[3], DN1, prefix=False)    # ca
-        g.carry(CZ, LTZ, ZC[3], DN1, prefix=False)    # cv
+        if kept is None:
+            g.carry(CZ, LTZ, ZC[3], DN1, prefix=False)    # cv
         # pre = (0, X0, X1, X2) + cu ; suf = (Y2, Y1, Y0, 0) + ca ; svw = (Z2, Z1, Z0, 0) + cv
         g.pk_add(XC[3], CX, None)
         g.pk_add(YC[3], CY, None)
-        g.pk_add(ZC[3], CZ, None)
+        if kept is None:
+            g.pk_add(ZC[3], CZ, None)
         for k in range(3):
             g.pk_add(XC[k], XC[k], CX)
             g.pk_add(YC[k], YC[k], CY)
-            g.pk_add(ZC[k], ZC[k], CZ)
+            if kept is None:
+                g.pk_add(ZC[k], ZC[k], CZ)
         pre = [XC[3], XC[0], XC[1], XC[2]]
         suf = [YC[2], YC[1], YC[0], YC[3]]
-        svw = [ZC[2], ZC[1], ZC[0], ZC[3]]
         for h in range(NP):
             g.pk_fma(GB[h], Wi[h], suf[h], GB[h])
         for h in range(NP):
             g.pk_fma(GV[h], Wi[h], pre[h], GV[h])
-        for h in range(NP):
-            g.pk_fma(GU[h], a[h], svw[h], GU[h])
+        if kept is None:
+            svw = [ZC[2], ZC[1], ZC[0], ZC[3]]
+            for h in range(NP):
+                g.pk_fma(GU[h], a[h], svw[h], GU[h])
         if last and not tests:
             return
         for h in range(NP):
@@ -392,26 +503,30 @@ def build():
             g.emit(f"s_bitcmp1_b32 {S_NH}, {2 * i}", kind="salu")
             g.emit(f"s_cbranch_scc1 {lab}", kind="branch")
             g.label(ret)
-            g.emit("s_nop 0", kind="salu")
             cold.append(("fwd", i, lab, ret, t))
 
     def block(tests):
+        saved = SAVED_MIXED if tests else SAVED_HOM
+        parks = not tests
         for i in range(T - 1, -1, -1):
-            beta_site(i, tests)
-        a, t = A, Tt
+            beta_site(i, tests, saved.get(i, ZC))
+            if parks and i + 1 in PARKED:  # w of site i (R[i + 1]) has just been read for the last time in this pass
+                park(i + 1, store=True)
+        a = A
         for i in range(T):
-            fwd_site(i, tests, a, t)
-            a, t = t, a
-        # the block's result: beta at its left edge
-        for h in range(NP):
-            g.mov64(B[h], R[0][h])
+            t = ZC if i == 0 else R[i]
+            # (site i's kept vector sits in R[i + 2], the registers of w of site i + 1: asked back as soon as the vector is used)
+            fwd_site(i, tests, a, t, ZC if i == 0 else saved.get(i), refill=i + 2 if parks and i + 2 in PARKED else None,
+                     wait=parks and i + 1 in PARKED)
+            a = t
+        # (the block's result, beta at its left edge, stays in R[0]: see the run's prologue)
 
     # ---- all-hom block ---------------------------------------------------------------------------------------------------
     block(False)
     g.emit(f"s_branch {nxt}", kind="branch")
     # ---- mixed block -----------------------------------------------------------------------------------------------------
     g.label(mixed)
-    g.emit("s_nop 1", kind="salu")
+    g.emit(f"s_and_b32 {S_NM}, {S_TMP}, 0x5555", kind="salu")   # bit 2i: site i is missing in some lane (only this body asks)
     block(True)
     g.label(nxt)
     g.emit(f"s_sub_i32 {BLK}, {BLK}, 1", kind="salu")
@@ -491,6 +606,8 @@ def build():
 
     g.label(done)
     g.emit("s_waitcnt vmcnt(0) lgkmcnt(0)", kind="wait")
+    for h in range(NP):
+        g.mov64(B[h], R[0][h])
     for i in range(4):
         g.emit(f"v_mov_b32_e32 {AN[i]}, {g.txt(quad_lane(PQ0, i))}", [AN[i]], [quad_lane(PQ0, i)])
         g.emit(f"v_mov_b32_e32 {AN[4 + i]}, {g.txt(quad_lane(PQ1, i))}", [AN[4 + i]], [quad_lane(PQ1, i)])
@@ -498,8 +615,47 @@ def build():
     return lines, nops, g.next_free
 
 
+def path_counts(lines):
+    """Instruction mix of one trip through the block loop, per kind of block: {"all-hom" | "mixed": {class: count}}.  The mixed
+    trip is the one whose sixteen tests all fall through (the cold bodies are out of line, behind the loop); both trips take the
+    checkpoint prefetch and skip the step into the next observation word (every second block takes its nine instructions)."""
+    def stem(ln):
+        return ln.split("_")[1] if ln.startswith(".Lphk_") else None
+
+    pos = {}
+    for n, ln in enumerate(lines):
+        if ln.endswith(":"):
+            pos.setdefault(stem(ln), n)
+    skip_from = next(n for n, ln in enumerate(lines) if ln.startswith("s_cbranch_scc0") and stem(ln.split()[1]) == "sameword")
+    enter = [ln for n, ln in enumerate(lines[pos["top"]:pos["mixed"]], pos["top"]) if not (skip_from < n < pos["sameword"])]
+    split = next(n for n, ln in enumerate(enter) if ln.startswith("s_cbranch_scc0") and stem(ln.split()[1]) == "mixed")
+    hom = enter[split + 1:]
+    enter = enter[:split + 1]
+    tail = lines[pos["next"]:next(n for n in range(pos["next"], len(lines)) if lines[n].startswith("s_cbranch_scc1")) + 1]
+    mixed = lines[pos["mixed"]:pos["next"]]
+    res = {}
+    for name, body in (("all-hom", enter + hom + tail), ("mixed", enter + mixed + tail)):
+        ins = [ln.split()[0] for ln in body if not ln.endswith(":")]
+        res[name] = {
+            "total": len(ins),
+            "vector": sum(m.startswith("v_") for m in ins),
+            "packed": sum(m.startswith("v_pk_") for m in ins),
+            "scalar": sum(m.startswith("s_") and not m.startswith(("s_cbranch", "s_branch", "s_nop", "s_waitcnt")) for m in ins),
+            "branch": sum(m.startswith(("s_cbranch", "s_branch")) for m in ins),
+            "s_nop": sum(m == "s_nop" for m in ins),
+            "waitcnt": sum(m == "s_waitcnt" for m in ins),
+            "LDS": sum(m.startswith("ds_") for m in ins),
+            "global": sum(m.startswith("global_") for m in ins),
+        }
+    return res
+
+
 def main():
     lines, nops, top = build()
+    for name, c in path_counts(lines).items():
+        print(f"{name} block: " + ", ".join(f"{k} {v}" for k, v in c.items()))
+    if len(sys.argv) > 1 and sys.argv[1] == "--report":
+        return
     out = sys.argv[1] if len(sys.argv) > 1 else "phlash_amd/csrc/sweep_run_k16r2.inc"
     ops_io = []
     for nm, var in (("b", "beta"), ("gb", "gb"), ("gd", "gd"), ("gu", "gu"), ("gv", "gv"), ("g1", "g1")):

@@ -18,6 +18,13 @@ The 16-site block loop of the posterior predictive simulator (float64, K at run 
     python scripts/loop_report.py phlash_amd/csrc/build/launch_simulate.o simulate_kernelILb1ELb0E 2000
     python scripts/loop_report.py phlash_amd/csrc/build/launch_simulate.o simulate_kernelILb0ELb1E 2000
 
+The sweeps of the headline shape (K = 16 float32, R = 2: serial Lb0, segmented Lb1).  Their run of hot blocks is the hand-written
+sequence of scripts/gen_sweep_asm.py, one loop that holds the all-hom body, the mixed body and, behind it, the cold bodies of het and
+missing sites, so the row of that loop (the longest one) is their sum; the instructions of ONE trip, per kind of block, are what
+``python scripts/gen_sweep_asm.py --report`` prints:
+
+    python scripts/loop_report.py phlash_amd/csrc/build/launch_bwd_f32_16.o bwd_kernelIfLi16ELi2ELi8ELi4ELb0 1500
+
 tests/test_layout.py imports ``kernel_loops`` to hold the sweeps' block loops to "no scratch access".
 """
 import os
@@ -81,6 +88,7 @@ def kernel_loops(obj, pat):
                 "salu": cnt(lambda m: m.startswith("s_") and not m.startswith("s_cbranch") and m not in ("s_branch", "s_waitcnt", "s_nop")),
                 "branch": cnt(lambda m: m.startswith("s_cbranch") or m == "s_branch"),
                 "waitcnt": cnt(lambda m: m == "s_waitcnt"),
+                "nop": cnt(lambda m: m == "s_nop"),
                 "lds": cnt(lambda m: m.startswith("ds_")),
                 "global": cnt(lambda m: m.startswith(("global_", "buffer_", "flat_"))),
                 "scratch": cnt(lambda m: m.startswith("scratch_")),
@@ -97,7 +105,7 @@ def main():
         for r in k["loops"]:
             if r["n"] >= min_n:
                 print(f"  loop [{r['lo']:5d},{r['hi']:5d}] {r['n']:5d} insts: VALU {r['valu']} (pk {r['pk']}, dpp {r['dpp']})  SALU {r['salu']}  "
-                      f"branch {r['branch']}  waitcnt {r['waitcnt']}  LDS {r['lds']}  global {r['global']}  scratch {r['scratch']}")
+                      f"branch {r['branch']}  waitcnt {r['waitcnt']}  s_nop {r['nop']}  LDS {r['lds']}  global {r['global']}  scratch {r['scratch']}")
 
 
 if __name__ == "__main__":
