@@ -158,7 +158,9 @@ def particle_to_params(x, pattern: str, theta: float):
     # geomspace(t1, tM, M-1)
     k = torch.arange(M - 1, dtype=F64) / (M - 2)
     t = torch.cat([torch.zeros(1, dtype=F64), torch.exp(torch.log(t1) + k * (torch.log(tM) - torch.log(t1)))])
-    c_ep = torch.nn.functional.softplus(x[2 : 2 + P])
+    # params.py:127 is jax.nn.softplus = logaddexp(x, 0); torch.nn.functional.softplus returns x itself above its threshold of 20
+    # (1e-10 relative just above it), which this line did until the sampler-side fuzz compared the two oracles there
+    c_ep = torch.logaddexp(x[2 : 2 + P], torch.zeros_like(x[2 : 2 + P]))
     c = torch.repeat_interleave(c_ep, torch.tensor(epochs))
     rho = (0.1 + 9.9 * torch.sigmoid(x[2 + P])) * theta
     return from_dm(t, c, theta, rho)

@@ -65,8 +65,13 @@ __device__ __forceinline__ Dual dclamp(Dual a, double lo, double hi) {
     return a;
 }
 __device__ __forceinline__ Dual dsoftplus(Dual a) {
-    // log(1 + e^x), threshold 20 as torch.nn.functional.softplus
-    if (a.v > 20.0) return a;
+    // log(1 + e^x) = jax.nn.softplus (params.py:127), which has no threshold: above 20, where log1p(e^x) would lose its last digits
+    // and then overflow, x + log1p(e^-x) with the derivative sigmoid(x).  (Until the sampler-side fuzz this branch returned x itself,
+    // as torch.nn.functional.softplus does: 1e-10 relative from the reference just above 20.)
+    if (a.v > 20.0) {
+        const double e = exp(-a.v);
+        return mk(a.v + log1p(e), a.d / (1.0 + e));
+    }
     const double e = exp(a.v);
     return mk(log1p(e), a.d * e / (1.0 + e));
 }
@@ -243,11 +248,11 @@ __device__ double log_prior_one(int P, double alpha, double beta, const double* 
     const double rot = 0.1 + 9.9 * sg;
     const double z = log(rot);
     double ret = -0.5 * z * z - 0.91893853320467274178;  // 0.5 log(2 pi)
-    // softplus as torch evaluates it (threshold 20): y > 20 ? y : log1p(exp(y)), derivative 1 : sigmoid(y)
+    // softplus without a threshold, as dsoftplus above: y > 20 ? y + log1p(exp(-y)) : log1p(exp(y)), derivative sigmoid(y)
     auto lc_of = [&](int i, double& dlc) {
         const double y = x[2 + i];
-        const double sp = y > 20.0 ? y : log1p(exp(y));
-        const double dsp = y > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-y));
+        const double sp = y > 20.0 ? y + log1p(exp(-y)) : log1p(exp(y));
+        const double dsp = 1.0 / (1.0 + exp(-y));
         dlc = dsp / sp;
         return log(sp);
     };
@@ -370,8 +375,8 @@ __global__ __launch_bounds__(128) void chain_rule_kernel(CRArgs A) {
         const double* x = A.x + b * D;
         if (t < P) {
             const double y = x[2 + t];
-            const double sp = y > 20.0 ? y : log1p(exp(y));
-            const double dsp = y > 20.0 ? 1.0 : 1.0 / (1.0 + exp(-y));
+            const double sp = y > 20.0 ? y + log1p(exp(-y)) : log1p(exp(y));
+            const double dsp = 1.0 / (1.0 + exp(-y));
             dls[t] = dsp / sp;
             lcs[t] = log(sp);
         }

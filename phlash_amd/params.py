@@ -163,7 +163,13 @@ class MCMCParams:
 
     @property
     def c(self):
-        return torch.nn.functional.softplus(self.c_tr)
+        # jax.nn.softplus (params.py:127) = logaddexp(x, 0) has no threshold; torch.nn.functional.softplus returns x itself above
+        # 20 (1e-10 relative just above it).  Above 20 the missing log1p(e^-x) is added, as csrc/param_map.hip does (derivative
+        # sigmoid(x)); at and below 20 the added term is an exact zero and the value keeps its bits.
+        x = self.c_tr
+        big = x > 20.0
+        tail = torch.log1p(torch.exp(-torch.where(big, x, torch.full_like(x, 20.0))))
+        return torch.nn.functional.softplus(x) + torch.where(big, tail, torch.zeros_like(tail))
 
     @property
     def log_c(self):
