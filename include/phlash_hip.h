@@ -276,6 +276,37 @@ int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens,
                     double* ll, void* logratio, void* stream);
 
+/* Pair counts (the reference has no counterpart): the full pair posterior summed along the row,
+ *   counts[b, s, i, j] = sum over the row's own scored sites t of xi_t(i, j),    xi_t(i, j) = P(z_prev = i, z_t = j | o),
+ * the expected number of moves from TMRCA state i (the ORIGIN, first index) to state j: the Baum-Welch transition statistic, the
+ * matrix phk_transitions reduces to (stay, up, down) per state reached.  Conventions of phk_transitions: z_0 ~ pi precedes site 0
+ * (it is z_prev of site 0), alpha_t is the forward vector after site t with alpha_{-1} = pi, beta_L = 1, a missing site has
+ * e = 1, the W warm-up sites are conditioned on and not counted, and there is no warm-up correction.  With A[i,j] = b_j (i > j),
+ * d_j (i = j), u_i v_j (i < j) and w = e_{o_t} .* beta_t,
+ *   xi_t(i, j) = alpha_{t-1}(i) A[i, j] w_t(j) / Z_t,      Z_t = the sum of the numerator over all (i, j),
+ * so every counted site adds exactly 1: counts[b, s] sums to the number of the row's own scored sites, min(lens, L) - W.  Its
+ * diagonal is the sum of stay_t, its strict-upper column sums that of up_t and its strict-lower ones that of down_t of
+ * phk_transitions; its column sums are the summed marginals of phk_posterior.  d_k contains "recombined and coalesced again in the
+ * same interval": the diagonal counts sites whose TMRCA STATE stays, not sites without a recombination.
+ *   counts     [B, S, K, K] double for both handle types, required unless W = L.  The sweep sums alpha_{t-1}(i) w_t(j) / Z_t --
+ *              float32 handles in float32, added into float64 every 64 sites; float64 handles in float64 -- and A[i, j], formed
+ *              in float64 from the parameter block (the factors as the kernels hold them), multiplies the float64 sum once;
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N] or NULL, exactly as phk_transitions: a site at or past its row's own length adds nothing; an
+ *              entry outside (W, L] is clamped and raises the bad-index flag.
+ * With W = L there is no scored site: ll = 0 and counts, where given, is zeros (it may be NULL).  params / prefold / inds /
+ * strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs, slabs (phk_set_workspace_limit) and stream ordering
+ * are phk_posterior's, with the pair-count sweep in the decode sweep's place (a hybrid plan runs as its serial half); the plan is
+ * read, never tuned or recorded.  Every unit of the sweep writes a float64 partial of its own in the call's workspace (K * K
+ * doubles per unit and sequence: part of the slab arithmetic, a large batch is cut into more slabs) and one kernel sums them in
+ * unit order: no atomics, the same bits for any slab size and for repeated calls under one plan; a serial and a segmented plan
+ * sum in different orders and may differ in the last bits.  Stream-ordered; no two calls on one handle may overlap.  The underflow
+ * flag is raised as by phk_loglik: re-evaluate after phk_set_rescale_interval(h, 1).  PHK_EINVAL, before anything is enqueued,
+ * for a NULL handle, NULL params / inds / ll, NULL counts with W < L, W outside [0, L]. */
+int phk_pair_counts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, const int64_t* lens, double* ll, double* counts,
+                    void* stream);
+
 /* Viterbi decoding (the reference has no counterpart): the single most probable hidden path of every sequence (b, s).
  * For a row o_0 .. o_{n-1} (n = the row's own length, see lens) with the convention of the forward recursion (z_0 ~ pi
  * precedes site 0, site t is step t + 1, a missing site has e = 1):

@@ -34,6 +34,7 @@ SIGNATURES = {
     "phk_predictive": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "phk_tracts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "phk_local_ratio": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "phk_pair_counts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "phk_viterbi": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "phk_sample_paths": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _vp, _vp, _i64, _vp]),
     "phk_simulate": (_i, [_i, _i, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_uint64, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),

@@ -25,6 +25,7 @@
 #include "loo_args.h"
 #include "tract_args.h"
 #include "local_args.h"
+#include "pairs_args.h"
 #include "simulate_args.h"
 
 namespace phk {
@@ -40,7 +41,8 @@ namespace phk {
     hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_loo_##tag(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st);     \
     hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st); \
-    hipError_t launch_local_##tag(int T, int nrm, const KArgs& a, const RArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_local_##tag(int T, int nrm, const KArgs& a, const RArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_pairs_##tag(int T, int nrm, const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -154,7 +156,7 @@ struct phk_handle {
     int K = 0, device = 0, dbl = 0;
     int64_t N = 0, L = 0, Lw = 0;
     uint32_t* packed = nullptr;
-    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops;
+    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops, pairs;
     int64_t ws_limit = 0;
     int force_R = 0, force_T = 0, nrm = DEFAULT_NRM;
     int mode = -1;     // -1 auto, 0 serial, 1 segmented
@@ -898,7 +900,7 @@ int phk_destroy(phk_handle* h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_fwd) (void)hipEventDestroy(h->ev_fwd);
     if (h->side) (void)hipStreamDestroy(h->side);
-    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops})
+    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops, &h->pairs})
         b->release();
     if (h->packed) (void)hipFree(h->packed);
     delete h;
@@ -1022,9 +1024,10 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
                                             "decode_kernel (serial sweep)", "decode_kernel (segment sweep)", "vit_fwd_kernel", "vit_back_kernel",
                                             "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)",
                                             "loo_kernel (serial sweep)", "loo_kernel (segment sweep)", "tract_kernel (serial sweep)",
-                                            "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)"};
+                                            "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)",
+                                            "pairs_kernel (serial sweep)", "pairs_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 17 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 19 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1562,6 +1565,9 @@ struct TransOut {
     const float* alt_prefold;
     void* logratio;  // ... into this output
     bool local;
+    // phk_pair_counts: the pair-count sweep (launch_pairs.hip) runs instead, into this output (double [B, S, K, K])
+    double* counts;
+    bool pairs;
 };
 
 // Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
@@ -1570,7 +1576,9 @@ struct TransOut {
 // tr != nullptr (phk_transitions): the same legs, slabs and stream ordering with the transition sweep (launch_trans.hip) in the
 // decode sweep's place; values, mean and marginals are unused then.  tr->loo (phk_predictive): the leave-one-out predictive sweep
 // (launch_loo.hip) in that place.  tr->tracts (phk_tracts): the tract-posterior sweep (launch_tract.hip) in that place.  tr->local
-// (phk_local_ratio): the local likelihood-ratio sweep (launch_local.hip) in that place.
+// (phk_local_ratio): the local likelihood-ratio sweep (launch_local.hip) in that place.  tr->pairs (phk_pair_counts): the pair-count
+// sweep (launch_pairs.hip) in that place, at bin = 1; its per-unit float64 partials are workspace of the call and part of the slab
+// arithmetic.
 static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                           const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                           double* ll, void* mean, void* marginals, void* stream, const TransOut* tr = nullptr) {
@@ -1587,7 +1595,8 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     if (tr && tr->local && !tr->logratio && W < h->L) return fail(PHK_EINVAL, "logratio is NULL: nothing to compute");
     if (tr && tr->local && tr->alt_prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
     if (tr && tr->local && tr->alt_prefold && (tr->astride_b % 7 != 0 || tr->astride_s % 7 != 0)) return fail(PHK_EINVAL, "alternative strides must be multiples of 7 (whole [7, K] blocks)");
-    if (tr && !tr->loo && !tr->tracts && !tr->local && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
+    if (tr && tr->pairs && !tr->counts && W < h->L) return fail(PHK_EINVAL, "counts is NULL: nothing to compute");
+    if (tr && !tr->loo && !tr->tracts && !tr->local && !tr->pairs && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
     if (!tr && !mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
     if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
@@ -1627,10 +1636,17 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     case k: lcl = h->dbl ? phk::launch_local_f64_##k : phk::launch_local_f32_##k; break;
     switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
 #undef PHK_CASE
+    typedef hipError_t (*prs_fn)(int, int, const phk::KArgs&, const phk::PArgs&, int, int, hipStream_t);
+    prs_fn prs = nullptr;
+#define PHK_CASE(k) \
+    case k: prs = h->dbl ? phk::launch_pairs_f64_##k : phk::launch_pairs_f32_##k; break;
+    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
+#undef PHK_CASE
+    const bool is_prs = tr && tr->pairs;
     const bool is_loo = tr && tr->loo;
     const bool is_trc = tr && tr->tracts;
     const bool is_lcl = tr && tr->local;
-    const char* const sweep_name = is_lcl ? "local-ratio" : is_trc ? "tract" : is_loo ? "predictive" : (tr ? "transition" : "decode");
+    const char* const sweep_name = is_prs ? "pair-count" : is_lcl ? "local-ratio" : is_trc ? "tract" : is_loo ? "predictive" : (tr ? "transition" : "decode");
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
@@ -1641,7 +1657,10 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
     // the checkpoint store is slabbed as for a gradient call
     int64_t Bs = B, Ss = S;
     {
-        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
+        // (pair counts: plus a [K, K] float64 partial per unit and sequence, sized for the plan with the most units -- the plan
+        // is chosen by the slab, so the slab cannot wait for it)
+        const int64_t units_max = std::max<int64_t>(1, std::max(n_units(h, 8, W), n_units(h, 16, W)));
+        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs + (is_prs ? units_max * K * K * (int64_t)sizeof(double) : 0);
         const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
         if (B * S > max_seq) {
             if (max_seq >= S) {
@@ -1665,6 +1684,9 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
         if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
     }
     const int units = plan.segmented ? (int)n_units(h, plan.T, W) : 0;
+    if (is_prs) {  // sized before anything of this call is enqueued
+        if (int rc = h->pairs.ensure((size_t)std::max(units, 1) * (size_t)nseq_launch * K * K * sizeof(double)); rc != PHK_OK) return rc;
+    }
 
     for (int64_t b0 = 0; b0 < B; b0 += Bs) {
         const int64_t nb = std::min(Bs, B - b0);
@@ -1756,11 +1778,16 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             ra.apfstride_s = ra.astride_s / 7 * 5;
             ra.alt_prefold = is_lcl && tr->alt_prefold ? tr->alt_prefold + (b0 * ra.apfstride_b + s0 * ra.apfstride_s) : nullptr;
             ra.logratio = is_lcl && tr->logratio ? (char*)tr->logratio + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
+            phk::PArgs pa;
+            pa.lens = tr ? tr->lens : nullptr;
+            pa.part = (double*)h->pairs.p;
+            pa.counts = is_prs && tr->counts ? tr->counts + (b0 * S + s0) * K * K : nullptr;
+            pa.row0 = 0;
             hipError_t e;
             if (!plan.segmented) {
                 e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-                e = is_lcl ? lcl(plan.T, h->nrm, a, ra, 0, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, 0, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
+                e = is_prs ? prs(plan.T, h->nrm, a, pa, 0, 256, st) : is_lcl ? lcl(plan.T, h->nrm, a, ra, 0, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, 0, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
                 if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", sweep_name, K, plan.T, hipGetErrorString(e));
                 continue;
             }
@@ -1773,7 +1800,7 @@ static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, 
             if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
             HIP_TRY(hipEventRecord(h->ev_join, h->side));
             HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            e = is_lcl ? lcl(plan.T, h->nrm, a, ra, units, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, units, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
+            e = is_prs ? prs(plan.T, h->nrm, a, pa, units, 256, st) : is_lcl ? lcl(plan.T, h->nrm, a, ra, units, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, units, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
             if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", sweep_name, K, plan.T, units, hipGetErrorString(e));
         }
     }
@@ -1812,6 +1839,15 @@ int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_
                     int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* logratio, void* stream) {
     const TransOut tr = {lens, nullptr, nullptr, nullptr, false, nullptr, 0, nullptr, false, alt_params, astride_b, astride_s, alt_prefold, logratio, true};
     return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+}
+
+int phk_pair_counts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, const int64_t* lens, double* ll, double* counts, void* stream) {
+    TransOut tr = {};
+    tr.lens = lens;
+    tr.counts = counts;
+    tr.pairs = true;
+    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, 1, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
 }
 
 // Viterbi decoding (phk_viterbi): the max-product forward kernel, then the traceback, per slab of the checkpoint store.  Like

@@ -7,7 +7,8 @@ from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sam
 ``phk_sample_paths``), the breakpoint track from its transition sweep (``PSMCKernel.transitions`` -> ``phk_transitions``) and
 the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``) and the
 tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``) and the local likelihood-ratio scans from its
-local-ratio sweep (``PSMCKernel.local_ratio`` -> ``phk_local_ratio``); this module only builds the models, pads ragged inputs,
+local-ratio sweep (``PSMCKernel.local_ratio`` -> ``phk_local_ratio``) and the expected transition matrix from its pair-count sweep
+(``PSMCKernel.pair_counts`` -> ``phk_pair_counts``); this module only builds the models, pads ragged inputs,
 averages, counts and run-length encodes.  There is no CPU path.
 """
 
@@ -322,6 +323,67 @@ def local_scan(dms, data, what: str = "theta", scales=(0.25, 0.5, 2.0, 4.0), win
     lrs = [lr[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
     comps = [x.sum(0) for x in lrs]
     return LocalScan(lrs, comps, tuple(sc), [sct[c.argmax(-1)] for c in comps])
+
+
+class TransitionCounts(NamedTuple):
+    """What ``transition_counts`` returns: float64 tensors on the device, origin state first."""
+
+    counts: torch.Tensor  # [M, M]: the mean over the models of per_model
+    expected: torch.Tensor  # [M, M]: the mean over the models of (row sums of per_model) * the model's own transition matrix
+    per_model: torch.Tensor  # [n_models, M, M]: expected moves from state i to state j, summed over every row of every contig
+
+
+def _dense_transition(pp: PSMCParams) -> torch.Tensor:
+    """[..., M, M] transition matrix of SMC' from its structured factors: b_j below the diagonal, d_j on it, u_i v_j above"""
+    b, d, u, v = (torch.as_tensor(getattr(pp, f), dtype=torch.float64) for f in ("b", "d", "u", "v"))
+    below = torch.tril(b[..., None, :].expand(b.shape + b.shape[-1:]), -1)
+    return below + torch.diag_embed(d) + torch.triu(u[..., :, None] * v[..., None, :], 1)
+
+
+def transition_counts(dms, data, window_size: int = 100, device=None, double_precision: bool = False) -> TransitionCounts:
+    """The expected M x M matrix of TMRCA-state transitions over all of ``data``, beside what the model's own transition kernel
+    would give: a calibration of the SMC' transition structure that does not depend on the emission check of
+    ``predictive_check``.
+
+    ``per_model[m, i, j]`` is the sum over every window of every row of P(z_prev = i, z_t = j | data) under model m, exact
+    (``PSMCKernel.pair_counts``): the expected number of moves from state i to state j, and the Baum-Welch transition statistic.
+    ``counts`` is its mean over the models.  ``expected`` is the mean over the models of rowsum_i(per_model) * A_model[i, j]:
+    what the model's transition matrix makes of the same posterior occupancy of the origin states.  ``counts / expected`` far
+    from 1 in row i says the data moves away from state i differently than the model does.  Both matrices sum to the number
+    of windows in ``data``.  The diagonal counts windows whose state stays: a recombination that coalesces again in the same
+    interval is not a move.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, and the padded windows count nothing (each row's
+        own length goes to the kernel, which masks them).
+    Returns ``TransitionCounts(counts, expected, per_model)``, float64 on the device.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.pair_counts(pp, torch.arange(rows.shape[0], device=dev), lens=lens)
+    per_model = out.counts.to(torch.float64).sum(1)  # [B, M, M]: every row of every contig
+    A = _dense_transition(PSMCParams(*(f[:, 0] for f in pp))).to(per_model.device)  # [B, M, M]
+    expected = (per_model.sum(-1, keepdim=True) * A).mean(0)
+    return TransitionCounts(per_model.mean(0), expected, per_model)
 
 
 def viterbi_tmrca(dm, data, window_size: int = 100, device=None, double_precision: bool = False):

@@ -345,6 +345,48 @@ class HipEngine:
             a = a[..., : self.K_user]
         return ll, c, a
 
+    def pair_counts(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, lens: torch.Tensor | None = None):
+        """Pair counts (``phk_pair_counts``): params / inds as ``run``.  Returns (ll [B, S] float64, counts [B, S, K, K] float64,
+        origin state first): the pair posterior P(z_prev = i, z_t = j | o) summed over every row's own scored sites, the expected
+        number of moves from state i to state j.  ``lens`` as ``transitions``.  Padded states (K below the compiled size) have no
+        mass; they are stripped."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        assert 0 <= int(warmup) <= self.L
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        pad_k = self.K - self.K_user
+        if pad_k:
+            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
+            pad[:, :, 4:6, :] = 1.0
+            params = torch.cat([params, pad], -1)
+        if lens is not None:
+            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
+            lens = lens.contiguous()
+        stream = torch.cuda.current_stream(self.device).cuda_stream
+        pf = None
+        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
+            p64 = params.contiguous()
+            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
+                                               None, ctypes.c_void_p(stream)))
+        else:
+            p = params.to(self.dtype).contiguous()
+        inds = inds.contiguous()
+        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
+        c = torch.empty((B, S, self.K, self.K), dtype=torch.float64, device=self.device)
+        rc = _lib.load().phk_pair_counts(
+            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
+            inds.data_ptr(), B, S, int(warmup), lens.data_ptr() if lens is not None else None, ll.data_ptr(), c.data_ptr(),
+            ctypes.c_void_p(stream),
+        )
+        _lib.check(rc)
+        if pad_k:
+            c = c[..., : self.K_user, : self.K_user]
+        return ll, c
+
     def predictive(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, bin: int = 1, lens: torch.Tensor | None = None):
         """Leave-one-out predictive decoding (``phk_predictive``): params / inds as ``run``.  Returns (ll [B, S] float64, track
         [B, S, nbin, 3] in the handle's float type) over bins of ``bin`` scored sites (nbin = ceil((L - warmup) / bin)): the

@@ -72,6 +72,16 @@ def _transitions_guarded(kern, *args, **kw):
     return out
 
 
+def _pair_counts_guarded(kern, *args, **kw):
+    """engine.pair_counts with the same safety net as ``_run_guarded`` (the pair-count sweep raises the same underflow flag)."""
+    out = kern._eng.pair_counts(*args, **kw)
+    if kern._eng.underflow_risk():
+        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
+        kern._eng.set_rescale_interval(1)
+        out = kern._eng.pair_counts(*args, **kw)
+    return out
+
+
 def _predictive_guarded(kern, *args, **kw):
     """engine.predictive with the same safety net as ``_run_guarded`` (the predictive sweep raises the same underflow flag)."""
     out = kern._eng.predictive(*args, **kw)
@@ -136,6 +146,13 @@ class Transitions(NamedTuple):
     ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
     changes: torch.Tensor  # [..., nbin, 2]: bin sums of the expected moves to an older / a younger state
     arrivals: torch.Tensor | None  # [..., nbin, 3, M]: bin means of (stay, up, down) per state, or None
+
+
+class PairCounts(NamedTuple):
+    """What ``PSMCKernel.pair_counts`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    counts: torch.Tensor  # [..., M, M] float64, origin state first: expected moves from state i to state j over the row's own scored sites
 
 
 class Predictive(NamedTuple):
@@ -382,6 +399,29 @@ class PSMCKernel:
             ll, c, a = _transitions_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens, arrivals=bool(arrivals))
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Transitions(strip(ll), strip(c), strip(a))
+
+    # ---- pair counts -----------------------------------------------------------------------------
+    def pair_counts(self, pp, index, *, lens=None) -> PairCounts:
+        """The pair posterior summed along the row: ``counts`` [..., M, M] float64 with counts[i, j] = the sum over the row's own
+        scored sites of P(z_prev = i, z_t = j | o), the expected number of moves from TMRCA state i (first index) to state j --
+        the matrix ``transitions`` reduces to (stay, up, down) per state reached, and the Baum-Welch transition statistic.  It
+        sums to the number of the row's own scored sites; row i held against row i of the model's transition matrix says whether
+        the transition structure fits the data.  Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as
+        ``loglik``).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <= L``): sites at or
+        past a row's own length add nothing.  Returns ``PairCounts(ll, counts)``, float64 device tensors for either
+        ``float_type``; no gradient."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        with torch.no_grad():
+            fields = [_as_tensor(a, self.device) for a in pp]
+            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            if lens is not None:
+                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                                       dtype=torch.int64, device=self.device)
+                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+            ll, c = _pair_counts_guarded(self, pa, inds, warmup=self.overlap, lens=lens)
+        return PairCounts(self._strip(ll, added_B, added_S), self._strip(c, added_B, added_S))
 
     # ---- leave-one-out predictive -------------------------------------------------------------
     def predictive(self, pp, index, *, bin: int = 1, lens=None) -> Predictive:

@@ -3,6 +3,7 @@
 from hipcc -Rpass-analysis=kernel-resource-usage (cross-compiles; no GPU needed).
 
     python scripts/kernel_resources.py f32 16 [extra hipcc flags ...]
+    python scripts/kernel_resources.py f32 16 --unit=launch_pairs [extra hipcc flags ...]     (a sweep's own translation unit)
 """
 import os
 import re
@@ -14,13 +15,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 def main():
     real, K = sys.argv[1], sys.argv[2]
-    extra = sys.argv[3:]
+    extra = [x for x in sys.argv[3:] if not x.startswith("--unit=")]
+    unit = ([x[7:] for x in sys.argv[3:] if x.startswith("--unit=")] or ["launch"])[0]
     ctype = {"f32": "float", "f64": "double"}[real]
     err = ""
-    for part, sched in ((1, []), (2, [])):  # the Makefile's two halves
+    for part, sched in ((1, []), (2, [])) if unit == "launch" else ((0, []),):  # the Makefile's two halves of launch.hip
         cmd = ["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fPIC", "-std=c++17",
                f"-DPHK_REAL={ctype}", f"-DPHK_K={K}", f"-DPHK_SUFFIX={real}_{K}", f"-DPHK_PART={part}",
-               "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "phlash_amd", "csrc", "launch.hip"),
+               "-Rpass-analysis=kernel-resource-usage", "-c", os.path.join(ROOT, "phlash_amd", "csrc", unit + ".hip"),
                "-o", "/dev/null"] + sched + extra
         err += subprocess.run(cmd, capture_output=True, text=True).stderr
     rows, cur = [], {}
