@@ -16,31 +16,20 @@
 // where its block fits in registers, it gives a 16-site block of float64 alphas 128 VGPRs, and it keeps every lane's
 // slice of a marginals row one 16- or 32-byte piece.
 #include "psmc_kernels.hip"
-#include "decode_args.h"
-
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
-
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
+#include "sweep_common.h"
 
 namespace phk {
 
-constexpr int DECODE_SPL = 4;  // states per lane (R = K / 4)
 // kernel ids of the decode sweep in the overrun record (KArgs::risk[1]; phk_underflow_risk names them)
 constexpr int OVERRUN_DECODE_SERIAL = 5;
 constexpr int OVERRUN_DECODE_SEG = 6;
-
-template <typename real, int K, int T>
-constexpr int decode_waves_per_simd() { return T * DECODE_SPL * (int)sizeof(real) <= 256 ? 2 : 1; }
 
 // SEG = false: one unit per sequence walks every block.  SEG = true: blockIdx.y picks a unit with the block range of the
 // segment sweep (unit 0: every segment up to the one holding the warm-up boundary), seeded from the beta scan's value at its
 // right edge.  The seeds left of the warm-up boundary are the plain beta (the scan does not know W), and decoding has no
 // warm-up correction, so every unit is independent.
 template <typename real, int K, int R, int T, int NRM, bool SEG>
-__global__ __launch_bounds__(NT_MAX, (decode_waves_per_simd<real, K, T>())) void decode_kernel(KArgs A, DArgs D) {
+__global__ __launch_bounds__(NT_MAX, (sweep_waves_per_simd<real>(T))) void decode_kernel(KArgs A, DArgs D) {
     using L = Lane<real, K, R>;
     using V = typename L::V;
     constexpr int SPL = L::SPL, NP = L::NP;
@@ -191,38 +180,6 @@ __global__ __launch_bounds__(NT_MAX, (decode_waves_per_simd<real, K, T>())) void
     if (risky && active && A.risk != nullptr) atomicOr(A.risk, FLAG_UNDERFLOW);
 }
 
-constexpr int DECODE_R = PHK_K / DECODE_SPL;
-
-template <int T, int NRM>
-static hipError_t decode_tn(const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, DECODE_R>;
-    const int64_t nseq = (a.seq_end > 0 ? a.seq_end : a.B * a.S) - a.seq_begin;
-    const int spb = nt / DECODE_R;
-    const size_t lds = (size_t)L::ETAB_STRIDE * nt * sizeof(PHK_REAL);
-    const dim3 block(nt);
-    if (units <= 0) {
-        hipLaunchKernelGGL((decode_kernel<PHK_REAL, PHK_K, DECODE_R, T, NRM, false>), dim3((unsigned)((nseq + spb - 1) / spb)), block, lds, st, a, d);
-    } else {
-        hipLaunchKernelGGL((decode_kernel<PHK_REAL, PHK_K, DECODE_R, T, NRM, true>), dim3((unsigned)((nseq + spb - 1) / spb), (unsigned)units), block, lds,
-                           st, a, d);
-    }
-    return hipGetLastError();
-}
-
-template <int T>
-static hipError_t decode_t(int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st) {
-    if (nrm == 1) return decode_tn<T, 1>(a, d, units, nt, st);
-    if (nrm == 2) return decode_tn<T, 2>(a, d, units, nt, st);
-    if (nrm == 4) return decode_tn<T, 4>(a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
-
-// T: the checkpoint spacing of the forward kernel that ran before; nrm: its rescale interval; units <= 0: one serial sweep per
-// sequence, else the segment layout of the segmented plan (KArgs::seg_blocks, bseg)
-hipError_t PHK_CAT(launch_decode_, PHK_SUFFIX)(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st) {
-    if (T == 8) return decode_t<8>(nrm, a, d, units, nt, st);
-    if (T == 16) return decode_t<16>(nrm, a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
+PHK_SWEEP_LAUNCHER(decode, DArgs, 1)
 
 }  // namespace phk

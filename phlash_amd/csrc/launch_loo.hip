@@ -14,38 +14,13 @@
 //
 // Per group three float64 sums per bin (every lane of the group holds the same bits); one writer per bin, no atomics.
 #include "psmc_kernels.hip"
-#include "loo_args.h"
-
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
-
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
+#include "sweep_common.h"
 
 namespace phk {
 
-constexpr int LOO_SPL = 4;  // states per lane (R = K / 4), as the decode sweep
 // kernel ids of the predictive sweep in the overrun record (KArgs::risk[1]; phk_underflow_risk names them)
 constexpr int OVERRUN_LOO_SERIAL = 12;
 constexpr int OVERRUN_LOO_SEG = 13;
-
-// sites whose alphas are held at once (see loo_kernel)
-template <typename real, int T>
-constexpr int loo_hold() { return sizeof(real) == 8 && T == 16 ? 4 : T; }
-template <typename real, int K, int T>
-constexpr int loo_waves_per_simd() { return loo_hold<real, T>() * LOO_SPL * (int)sizeof(real) <= 256 ? 2 : 1; }
-
-// own length of the sequence's data row, clamped to (W, Ltot] (out of range: FLAG_BAD_INDEX, as a bad chunk index)
-__device__ __forceinline__ int64_t loo_len(const KArgs& A, const LArgs& D, int64_t row) {
-    if (D.lens == nullptr) return A.Ltot;
-    int64_t n = D.lens[row];
-    if (n <= A.W || n > A.Ltot) {
-        if (A.risk != nullptr) atomicOr(A.risk, FLAG_BAD_INDEX);
-        n = n > A.Ltot ? A.Ltot : A.W + 1;
-    }
-    return n;
-}
 
 __device__ __forceinline__ float loo_log(float x) { return logf(x); }
 __device__ __forceinline__ double loo_log(double x) { return log(x); }
@@ -53,7 +28,7 @@ __device__ __forceinline__ double loo_log(double x) { return log(x); }
 // SEG = false: one unit per sequence walks every block.  SEG = true: blockIdx.y picks a unit of the segment layout, seeded from
 // the beta scan's value at its right edge (see decode_kernel: the units, their bins and their seeds are the same).
 template <typename real, int K, int R, int T, int NRM, bool SEG>
-__global__ __launch_bounds__(NT_MAX, (loo_waves_per_simd<real, K, T>())) void loo_kernel(KArgs A, LArgs D) {
+__global__ __launch_bounds__(NT_MAX, (sweep_waves_per_simd<real>(sweep_hold<real, T>()))) void loo_kernel(KArgs A, LArgs D) {
     using L = Lane<real, K, R>;
     using V = typename L::V;
     constexpr int SPL = L::SPL, NP = L::NP;
@@ -63,7 +38,7 @@ __global__ __launch_bounds__(NT_MAX, (loo_waves_per_simd<real, K, T>())) void lo
     // unrolled float64 logarithms take more than that gives back: the compiler's report for K = 16 is 256 VGPRs + 114 AGPR
     // copies at one wave per SIMD for a whole block, 256 VGPRs + 116 bytes of scratch for a half, 186 VGPRs and neither for
     // a quarter.  A piece re-runs the forward steps of the block's sites before it: 24 extra steps per block of 16.
-    constexpr int H = loo_hold<real, T>();
+    constexpr int H = sweep_hold<real, T>();
     static_assert(T % H == 0 && H % NRM == 0, "pieces / rescale schedule");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -119,7 +94,7 @@ __global__ __launch_bounds__(NT_MAX, (loo_waves_per_simd<real, K, T>())) void lo
 
     const int64_t row = checked_row(A, ss);
     const uint32_t* words = A.packed + row * A.Lw;
-    const int64_t len = loo_len(A, D, row);
+    const int64_t len = sweep_len(A, D, row);
     const int64_t ck_step = nseq * K;
     const real* ck = (const real*)A.ckpt + L::ck_lane(nseq, seq, rank);
     constexpr int RISK_EXP = sizeof(real) == 4 ? RISK_EXP_F32 : RISK_EXP_F64;
@@ -239,38 +214,6 @@ __global__ __launch_bounds__(NT_MAX, (loo_waves_per_simd<real, K, T>())) void lo
     if (risky && active && A.risk != nullptr) atomicOr(A.risk, FLAG_UNDERFLOW);
 }
 
-constexpr int LOO_R = PHK_K / LOO_SPL;
-
-template <int T, int NRM>
-static hipError_t loo_tn(const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, LOO_R>;
-    const int64_t nseq = (a.seq_end > 0 ? a.seq_end : a.B * a.S) - a.seq_begin;
-    const int spb = nt / LOO_R;
-    const size_t lds = (size_t)L::ETAB_STRIDE * nt * sizeof(PHK_REAL);
-    const dim3 block(nt);
-    if (units <= 0) {
-        hipLaunchKernelGGL((loo_kernel<PHK_REAL, PHK_K, LOO_R, T, NRM, false>), dim3((unsigned)((nseq + spb - 1) / spb)), block, lds, st, a, d);
-    } else {
-        hipLaunchKernelGGL((loo_kernel<PHK_REAL, PHK_K, LOO_R, T, NRM, true>), dim3((unsigned)((nseq + spb - 1) / spb), (unsigned)units), block, lds,
-                           st, a, d);
-    }
-    return hipGetLastError();
-}
-
-template <int T>
-static hipError_t loo_t(int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st) {
-    if (nrm == 1) return loo_tn<T, 1>(a, d, units, nt, st);
-    if (nrm == 2) return loo_tn<T, 2>(a, d, units, nt, st);
-    if (nrm == 4) return loo_tn<T, 4>(a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
-
-// T: the checkpoint spacing of the forward kernel that ran before; nrm: its rescale interval; units <= 0: one serial sweep per
-// sequence, else the segment layout of the segmented plan (KArgs::seg_blocks, bseg)
-hipError_t PHK_CAT(launch_loo_, PHK_SUFFIX)(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st) {
-    if (T == 8) return loo_t<8>(nrm, a, d, units, nt, st);
-    if (T == 16) return loo_t<16>(nrm, a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
+PHK_SWEEP_LAUNCHER(loo, LArgs, 1)
 
 }  // namespace phk

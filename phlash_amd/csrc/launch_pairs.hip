@@ -26,21 +26,14 @@
 // without a scored site leaves zeros); the finalize kernel sums the units in index order: one writer, no atomics, the same bits
 // for any slab.
 #include "psmc_kernels.hip"
-#include "pairs_args.h"
+#include "sweep_common.h"
 
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
 #ifndef PHK_PAIRS_MFMA
 #define PHK_PAIRS_MFMA 1  // A/B (scripts/pair_counts_timing.py): 0 = K = 16 float32 runs the plain template like every other (real, K)
 #endif
 
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
-
 namespace phk {
 
-constexpr int PAIRS_SPL = 4;  // states per lane (R = K / 4), as the transition sweep
 // kernel ids of the pair-count sweep in the overrun record (KArgs::risk[1]; phk_underflow_risk names them)
 constexpr int OVERRUN_PAIRS_SERIAL = 18;
 constexpr int OVERRUN_PAIRS_SEG = 19;
@@ -62,17 +55,6 @@ constexpr bool pairs_mfma() { return PHK_PAIRS_MFMA != 0 && sizeof(real) == 4 &&
 // origin rows per launch of the plain template: what leaves the object without scratch at two waves per SIMD
 template <typename real, int K>
 constexpr int pairs_rt() { return sizeof(real) == 8 ? 4 : (K <= 16 ? K : 8); }
-
-// own length of the sequence's data row, clamped to (W, Ltot] (out of range: FLAG_BAD_INDEX, as a bad chunk index)
-__device__ __forceinline__ int64_t pairs_len(const KArgs& A, const PArgs& D, int64_t row) {
-    if (D.lens == nullptr) return A.Ltot;
-    int64_t n = D.lens[row];
-    if (n <= A.W || n > A.Ltot) {
-        if (A.risk != nullptr) atomicOr(A.risk, FLAG_BAD_INDEX);
-        n = n > A.Ltot ? A.Ltot : A.W + 1;
-    }
-    return n;
-}
 
 // lane `src` of this lane's group of R
 template <int R>
@@ -146,7 +128,7 @@ __global__ __launch_bounds__(NT_MAX, 2) void pairs_kernel(KArgs A, PArgs D) {
 
     const int64_t row = checked_row(A, ss);
     const uint32_t* words = A.packed + row * A.Lw;
-    const int64_t len = pairs_len(A, D, row);
+    const int64_t len = sweep_len(A, D, row);
     const int64_t ck_step = nseq * K;
     const real* ck = (const real*)A.ckpt + L::ck_lane(nseq, seq, rank);
     constexpr int RISK_EXP = sizeof(real) == 4 ? RISK_EXP_F32 : RISK_EXP_F64;
@@ -336,37 +318,25 @@ __global__ void pairs_finalize_kernel(KArgs A, PArgs D, int units) {
     D.counts[oseq * (K * K) + ij] = s * aij;
 }
 
-constexpr int PAIRS_R = PHK_K / PAIRS_SPL;
-
 template <int T, int NRM>
 static hipError_t pairs_tn(const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, PAIRS_R>;
+    using L = Lane<PHK_REAL, PHK_K, SWEEP_R>;
     const int64_t nseq = (a.seq_end > 0 ? a.seq_end : a.B * a.S) - a.seq_begin;
-    const int spb = nt / PAIRS_R;
+    const int spb = nt / SWEEP_R;
     const size_t lds = (size_t)L::ETAB_STRIDE * nt * sizeof(PHK_REAL);
-    const dim3 block(nt);
+    const dim3 grid((unsigned)((nseq + spb - 1) / spb), (unsigned)(units <= 0 ? 1 : units)), block(nt);
     constexpr int step = pairs_mfma<PHK_REAL, PHK_K>() ? PHK_K : pairs_rt<PHK_REAL, PHK_K>();
     for (int row0 = 0; row0 < PHK_K; row0 += step) {  // one launch per row tile
         PArgs dd = d;
         dd.row0 = row0;
-        if (units <= 0) {
-            hipLaunchKernelGGL((pairs_kernel<PHK_REAL, PHK_K, PAIRS_R, T, NRM, false>), dim3((unsigned)((nseq + spb - 1) / spb)), block, lds, st, a, dd);
-        } else {
-            hipLaunchKernelGGL((pairs_kernel<PHK_REAL, PHK_K, PAIRS_R, T, NRM, true>), dim3((unsigned)((nseq + spb - 1) / spb), (unsigned)units), block,
-                               lds, st, a, dd);
-        }
+        if (units <= 0) hipLaunchKernelGGL((pairs_kernel<PHK_REAL, PHK_K, SWEEP_R, T, NRM, false>), grid, block, lds, st, a, dd);
+        else hipLaunchKernelGGL((pairs_kernel<PHK_REAL, PHK_K, SWEEP_R, T, NRM, true>), grid, block, lds, st, a, dd);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }
     return hipSuccess;
 }
 
-template <int T>
-static hipError_t pairs_t(int nrm, const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st) {
-    if (nrm == 1) return pairs_tn<T, 1>(a, d, units, nt, st);
-    if (nrm == 2) return pairs_tn<T, 2>(a, d, units, nt, st);
-    if (nrm == 4) return pairs_tn<T, 4>(a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
+PHK_SWEEP_DISPATCH(pairs, PArgs)
 
 // T: the checkpoint spacing of the forward kernel that ran before; nrm: its rescale interval; units <= 0: one serial sweep per
 // sequence, else the segment layout of the segmented plan (KArgs::seg_blocks, bseg).  Zeroes the partials, sweeps, finalizes.
@@ -376,9 +346,7 @@ hipError_t PHK_CAT(launch_pairs_, PHK_SUFFIX)(int T, int nrm, const KArgs& a, co
     const int nu = units > 0 ? units : 1;
     hipError_t e = hipMemsetAsync(d.part, 0, (size_t)nu * (size_t)nseq * PHK_K * PHK_K * sizeof(double), st);
     if (e != hipSuccess) return e;
-    if (T == 8) e = pairs_t<8>(nrm, a, d, units, nt, st);
-    else if (T == 16) e = pairs_t<16>(nrm, a, d, units, nt, st);
-    else return hipErrorInvalidValue;
+    e = pairs_any(T, nrm, a, d, units, nt, st);
     if (e != hipSuccess) return e;
     const int64_t n = nseq * PHK_K * PHK_K;
     hipLaunchKernelGGL((pairs_finalize_kernel<PHK_REAL, PHK_K>), dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, a, d, nu);

@@ -24,18 +24,10 @@
 //
 // Lanes per sequence: R = K / 4 (4 states per lane) for every (real, K), as the posterior-decoding sweep and Viterbi.
 #include "psmc_kernels.hip"
-#include "sample_args.h"
-
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
-
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
+#include "sweep_common.h"
 
 namespace phk {
 
-constexpr int SAMPLE_SPL = 4;  // states per lane (R = K / 4)
 // kernel id in the overrun record (KArgs::risk[1]; phk_underflow_risk names it)
 constexpr int OVERRUN_SAMPLE_BACK = 9;
 
@@ -44,8 +36,6 @@ constexpr int OVERRUN_SAMPLE_BACK = 9;
 template <typename real, int K>
 constexpr int sample_ns() { return sizeof(real) == 8 || K == 4 ? 2 : 4; }
 
-template <typename real, int K, int T>
-constexpr int sample_waves_per_simd() { return T * SAMPLE_SPL * (int)sizeof(real) <= 256 ? 2 : 1; }
 
 template <int CTRL>
 __device__ __forceinline__ int dppi_(int x) {
@@ -91,7 +81,7 @@ struct SampleLane {
     using L = Lane<real, K, R>;
     using V = typename L::V;
     static constexpr int SPL = L::SPL, NP = L::NP;
-    static_assert(SPL == SAMPLE_SPL, "four states per lane");
+    static_assert(SPL == SWEEP_SPL, "four states per lane");
     real u[SPL];
     int k0;
 
@@ -137,7 +127,7 @@ struct SampleLane {
 };
 
 template <typename real, int K, int R, int T, int NRM, int NS>
-__global__ __launch_bounds__(NT_MAX, (sample_waves_per_simd<real, K, T>())) void sample_back_kernel(KArgs A, SArgs D) {
+__global__ __launch_bounds__(NT_MAX, (sweep_waves_per_simd<real>(T))) void sample_back_kernel(KArgs A, SArgs D) {
     using L = Lane<real, K, R>;
     using V = typename L::V;
     constexpr int SPL = L::SPL, NP = L::NP;
@@ -279,19 +269,17 @@ __global__ __launch_bounds__(NT_MAX, (sample_waves_per_simd<real, K, T>())) void
     if (!ok && active && A.risk != nullptr) atomicOr(A.risk, FLAG_UNDERFLOW);
 }
 
-constexpr int SAMPLE_R = PHK_K / SAMPLE_SPL;
-
 template <int T, int NRM, int NS>
 static hipError_t sample_tnn(const KArgs& a, const SArgs& d, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, SAMPLE_R>;
+    using L = Lane<PHK_REAL, PHK_K, SWEEP_R>;
     const int64_t nseq = a.B * a.S;
-    const int spb = nt / SAMPLE_R;
+    const int spb = nt / SWEEP_R;
     const int64_t groups = (d.n_samples + NS - 1) / NS;
     if (groups > 65535) return hipErrorInvalidValue;
     // emission tables + the factors by state (sample_back_kernel: fac)
-    const size_t lds = ((size_t)L::ETAB_STRIDE + 3 * SAMPLE_SPL) * nt * sizeof(PHK_REAL);
+    const size_t lds = ((size_t)L::ETAB_STRIDE + 3 * SWEEP_SPL) * nt * sizeof(PHK_REAL);
     const dim3 grid((unsigned)((nseq + spb - 1) / spb), (unsigned)groups), block(nt);
-    hipLaunchKernelGGL((sample_back_kernel<PHK_REAL, PHK_K, SAMPLE_R, T, NRM, NS>), grid, block, lds, st, a, d);
+    hipLaunchKernelGGL((sample_back_kernel<PHK_REAL, PHK_K, SWEEP_R, T, NRM, NS>), grid, block, lds, st, a, d);
     return hipGetLastError();
 }
 

@@ -14,42 +14,18 @@
 // Rows of their own length (TArgs::lens): every sequence of a launch walks the same blocks; a site at or past the row's own
 // length is added with weight 0 (a select, not a divergent bound) and is not counted in the bin's mean.
 #include "psmc_kernels.hip"
-#include "trans_args.h"
-
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
-
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
+#include "sweep_common.h"
 
 namespace phk {
 
-constexpr int TRANS_SPL = 4;  // states per lane (R = K / 4), as the decode sweep
 // kernel ids of the transition sweep in the overrun record (KArgs::risk[1]; phk_underflow_risk names them)
 constexpr int OVERRUN_TRANS_SERIAL = 10;
 constexpr int OVERRUN_TRANS_SEG = 11;
 
-template <typename real, int T>
-constexpr int trans_hold() { return sizeof(real) == 8 && T == 16 ? 4 : T; }
-template <typename real, int K, int T>
-constexpr int trans_waves_per_simd() { return trans_hold<real, T>() * TRANS_SPL * (int)sizeof(real) <= 256 ? 2 : 1; }
-
-// own length of the sequence's data row, clamped to (W, Ltot] (out of range: FLAG_BAD_INDEX, as a bad chunk index)
-__device__ __forceinline__ int64_t trans_len(const KArgs& A, const TArgs& D, int64_t row) {
-    if (D.lens == nullptr) return A.Ltot;
-    int64_t n = D.lens[row];
-    if (n <= A.W || n > A.Ltot) {
-        if (A.risk != nullptr) atomicOr(A.risk, FLAG_BAD_INDEX);
-        n = n > A.Ltot ? A.Ltot : A.W + 1;
-    }
-    return n;
-}
-
 // SEG = false: one unit per sequence walks every block.  SEG = true: blockIdx.y picks a unit of the segment layout, seeded from
 // the beta scan's value at its right edge (see decode_kernel: the units, their bins and their seeds are the same).
 template <typename real, int K, int R, int T, int NRM, bool SEG>
-__global__ __launch_bounds__(NT_MAX, (trans_waves_per_simd<real, K, T>())) void trans_kernel(KArgs A, TArgs D) {
+__global__ __launch_bounds__(NT_MAX, (sweep_waves_per_simd<real>(sweep_hold<real, T>()))) void trans_kernel(KArgs A, TArgs D) {
     using L = Lane<real, K, R>;
     using V = typename L::V;
     constexpr int SPL = L::SPL, NP = L::NP;
@@ -58,7 +34,7 @@ __global__ __launch_bounds__(NT_MAX, (trans_waves_per_simd<real, K, T>())) void 
     // and the pair term's scans beside 16 float64 alphas do not fit 256 VGPRs, and neither does a half: an 8-site float64
     // block takes 240 as it is, and the checkpoint kept for the second piece tips it into scratch.  A piece re-runs the
     // forward steps of the block's sites before it: 24 extra steps per block of 16.
-    constexpr int H = trans_hold<real, T>();
+    constexpr int H = sweep_hold<real, T>();
     static_assert(T % H == 0 && H % NRM == 0, "pieces / rescale schedule");
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const int tid = threadIdx.x;
@@ -114,7 +90,7 @@ __global__ __launch_bounds__(NT_MAX, (trans_waves_per_simd<real, K, T>())) void 
 
     const int64_t row = checked_row(A, ss);
     const uint32_t* words = A.packed + row * A.Lw;
-    const int64_t len = trans_len(A, D, row);
+    const int64_t len = sweep_len(A, D, row);
     const int64_t ck_step = nseq * K;
     const real* ck = (const real*)A.ckpt + L::ck_lane(nseq, seq, rank);
     constexpr int RISK_EXP = sizeof(real) == 4 ? RISK_EXP_F32 : RISK_EXP_F64;
@@ -254,38 +230,6 @@ __global__ __launch_bounds__(NT_MAX, (trans_waves_per_simd<real, K, T>())) void 
     if (risky && active && A.risk != nullptr) atomicOr(A.risk, FLAG_UNDERFLOW);
 }
 
-constexpr int TRANS_R = PHK_K / TRANS_SPL;
-
-template <int T, int NRM>
-static hipError_t trans_tn(const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, TRANS_R>;
-    const int64_t nseq = (a.seq_end > 0 ? a.seq_end : a.B * a.S) - a.seq_begin;
-    const int spb = nt / TRANS_R;
-    const size_t lds = (size_t)L::ETAB_STRIDE * nt * sizeof(PHK_REAL);
-    const dim3 block(nt);
-    if (units <= 0) {
-        hipLaunchKernelGGL((trans_kernel<PHK_REAL, PHK_K, TRANS_R, T, NRM, false>), dim3((unsigned)((nseq + spb - 1) / spb)), block, lds, st, a, d);
-    } else {
-        hipLaunchKernelGGL((trans_kernel<PHK_REAL, PHK_K, TRANS_R, T, NRM, true>), dim3((unsigned)((nseq + spb - 1) / spb), (unsigned)units), block, lds,
-                           st, a, d);
-    }
-    return hipGetLastError();
-}
-
-template <int T>
-static hipError_t trans_t(int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st) {
-    if (nrm == 1) return trans_tn<T, 1>(a, d, units, nt, st);
-    if (nrm == 2) return trans_tn<T, 2>(a, d, units, nt, st);
-    if (nrm == 4) return trans_tn<T, 4>(a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
-
-// T: the checkpoint spacing of the forward kernel that ran before; nrm: its rescale interval; units <= 0: one serial sweep per
-// sequence, else the segment layout of the segmented plan (KArgs::seg_blocks, bseg)
-hipError_t PHK_CAT(launch_trans_, PHK_SUFFIX)(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st) {
-    if (T == 8) return trans_t<8>(nrm, a, d, units, nt, st);
-    if (T == 16) return trans_t<16>(nrm, a, d, units, nt, st);
-    return hipErrorInvalidValue;
-}
+PHK_SWEEP_LAUNCHER(trans, TArgs, 1)
 
 }  // namespace phk

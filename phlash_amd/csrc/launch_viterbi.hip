@@ -28,18 +28,10 @@
 //
 // Lanes per sequence: R = K / 4 (4 states per lane) for every (real, K), as the posterior-decoding sweep.
 #include "psmc_kernels.hip"
-#include "viterbi_args.h"
-
-#ifndef PHK_REAL
-#error "compile with -DPHK_REAL=float|double -DPHK_K=<K> -DPHK_SUFFIX=<tag>"
-#endif
-
-#define PHK_CAT2(a, b) a##b
-#define PHK_CAT(a, b) PHK_CAT2(a, b)
+#include "sweep_common.h"
 
 namespace phk {
 
-constexpr int VIT_SPL = 4;  // states per lane (R = K / 4)
 // sites per block: a divisor of the 16 sites of an observation word.  The traceback keeps a block's delta vectors in registers:
 // 16 x 4 float32 states are 64 VGPRs, and 8 float64 sites the same (with 16 the float64 kernels took 256 VGPRs and 70 AGPR copies)
 template <typename real>
@@ -58,7 +50,7 @@ template <typename real, int K, int R>
 struct VitLane {
     using L = Lane<real, K, R>;
     static constexpr int SPL = L::SPL;
-    static_assert(SPL == VIT_SPL, "four states per lane");
+    static_assert(SPL == SWEEP_SPL, "four states per lane");
     real b[SPL], d[SPL], u[SPL], v[SPL];
     const real* etab;
     int rank, k0;
@@ -193,17 +185,6 @@ struct VitLane {
     }
 };
 
-// own length of the sequence's data row, clamped to (W, Ltot] (out of range: FLAG_BAD_INDEX, as a bad chunk index)
-__device__ __forceinline__ int64_t vit_len(const KArgs& A, const VArgs& D, int64_t row) {
-    if (D.lens == nullptr) return A.Ltot;
-    int64_t n = D.lens[row];
-    if (n <= A.W || n > A.Ltot) {
-        if (A.risk != nullptr) atomicOr(A.risk, FLAG_BAD_INDEX);
-        n = n > A.Ltot ? A.Ltot : A.W + 1;
-    }
-    return n;
-}
-
 template <typename real, int K, int R, int T, int NRM>
 __global__ __launch_bounds__(NT_MAX) void vit_fwd_kernel(KArgs A, VArgs D) {
     using L = Lane<real, K, R>;
@@ -229,7 +210,7 @@ __global__ __launch_bounds__(NT_MAX) void vit_fwd_kernel(KArgs A, VArgs D) {
     vl.init(lane, rank);
 
     const int64_t row = checked_row(A, ss);
-    const int64_t n = vit_len(A, D, row);
+    const int64_t n = sweep_len(A, D, row);
     const uint32_t* words = A.packed + row * A.Lw;
     const int nblk = (int)((A.Ltot + T - 1) / T);
     const int64_t ck_step = nseq * K;
@@ -304,7 +285,7 @@ __global__ __launch_bounds__(NT_MAX) void vit_back_kernel(KArgs A, VArgs D) {
     vl.init(lane, rank);
 
     const int64_t row = checked_row(A, ss);
-    const int64_t n = vit_len(A, D, row);
+    const int64_t n = sweep_len(A, D, row);
     const int64_t Lt = A.Ltot, W = A.W;
     const uint32_t* words = A.packed + row * A.Lw;
     const int nblk = (int)((Lt + T - 1) / T);
@@ -388,20 +369,18 @@ __global__ __launch_bounds__(NT_MAX) void vit_back_kernel(KArgs A, VArgs D) {
     }
 }
 
-constexpr int VIT_R = PHK_K / VIT_SPL;
-
 template <int NRM>
 static hipError_t viterbi_n(const KArgs& a, const VArgs& d, int nt, hipStream_t st) {
-    using L = Lane<PHK_REAL, PHK_K, VIT_R>;
+    using L = Lane<PHK_REAL, PHK_K, SWEEP_R>;
     const int64_t nseq = a.B * a.S;
-    const int spb = nt / VIT_R;
+    const int spb = nt / SWEEP_R;
     const size_t lds = (size_t)L::ETAB_STRIDE * nt * sizeof(PHK_REAL);
     const dim3 grid((unsigned)((nseq + spb - 1) / spb)), block(nt);
-    hipLaunchKernelGGL((vit_fwd_kernel<PHK_REAL, PHK_K, VIT_R, VIT_T, NRM>), grid, block, lds, st, a, d);
+    hipLaunchKernelGGL((vit_fwd_kernel<PHK_REAL, PHK_K, SWEEP_R, VIT_T, NRM>), grid, block, lds, st, a, d);
     hipError_t e = hipGetLastError();
     if (e != hipSuccess) return e;
-    const size_t lds_back = lds + (size_t)3 * VIT_SPL * nt * sizeof(PHK_REAL);  // + the factors by state (vit_back_kernel: fac)
-    hipLaunchKernelGGL((vit_back_kernel<PHK_REAL, PHK_K, VIT_R, VIT_T, NRM>), grid, block, lds_back, st, a, d);
+    const size_t lds_back = lds + (size_t)3 * SWEEP_SPL * nt * sizeof(PHK_REAL);  // + the factors by state (vit_back_kernel: fac)
+    hipLaunchKernelGGL((vit_back_kernel<PHK_REAL, PHK_K, SWEEP_R, VIT_T, NRM>), grid, block, lds_back, st, a, d);
     return hipGetLastError();
 }
 

@@ -9,7 +9,6 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cmath>
-#include <cstring>
 #include <map>
 #include <new>
 #include <vector>
@@ -18,14 +17,7 @@
 #define PHK_WITH_PACK 1
 #include "psmc_kernels.hip"
 #include "step_args.h"
-#include "decode_args.h"
-#include "viterbi_args.h"
-#include "sample_args.h"
-#include "trans_args.h"
-#include "loo_args.h"
-#include "tract_args.h"
-#include "local_args.h"
-#include "pairs_args.h"
+#include "sweep_args.h"
 #include "simulate_args.h"
 
 namespace phk {
@@ -196,19 +188,17 @@ struct Launchers {
     fin_fn fin = nullptr;
 };
 
+// launch_<stem>_<real>_<K> of the handle's (real, K); null where K is not compiled in
+#define PHK_PICK_K(stem, h, k) (h)->K == k ? ((h)->dbl ? &phk::launch_##stem##_f64_##k : &phk::launch_##stem##_f32_##k)
+#define PHK_PICK(stem, h) \
+    (PHK_PICK_K(stem, h, 4) : PHK_PICK_K(stem, h, 8) : PHK_PICK_K(stem, h, 16) : PHK_PICK_K(stem, h, 32) : PHK_PICK_K(stem, h, 64) : nullptr)
+
 bool pick_launchers(const phk_handle* h, Launchers* l) {
-#define PHK_CASE(k)                                                                    \
-    case k:                                                                            \
-        l->fwd = h->dbl ? phk::launch_fwd_f64_##k : phk::launch_fwd_f32_##k;           \
-        l->bwd = h->dbl ? phk::launch_bwd_f64_##k : phk::launch_bwd_f32_##k;           \
-        l->bscan = h->dbl ? phk::launch_bscan_f64_##k : phk::launch_bscan_f32_##k;     \
-        l->fin = h->dbl ? phk::launch_finalize_f64_##k : phk::launch_finalize_f32_##k; \
-        return true;
-    switch (h->K) {
-        PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64)
-    }
-#undef PHK_CASE
-    return false;
+    l->fwd = PHK_PICK(fwd, h);
+    l->bwd = PHK_PICK(bwd, h);
+    l->bscan = PHK_PICK(bscan, h);
+    l->fin = PHK_PICK(finalize, h);
+    return l->fwd != nullptr;
 }
 
 // the handles whose sweeps have the hand-written block-run sequence (psmc_kernels.hip, PHK_ASM_RUN): K = 16, float32 kernels (R = 2 sweeps)
@@ -449,6 +439,26 @@ int scan_prio_for(const phk_handle* h, const Plan& plan) {
     return (plan.R2 == 16 && !plan.segmented && h->nonhom_frac > SCAN_PRIO_MIN_NONHOM) ? 2 : 0;
 }
 
+// Iteration budgets (KArgs::loop_budget): twice what a healthy wave needs, from the row length alone, times the scale
+// phk_set_loop_budget_scale gave the slot's kernel.  The forward kernel and the beta scan make one outer iteration per
+// 64-site piece (the ragged pieces at the warm-up boundary and the row's end a few more: one per block / word), a serial sweep
+// one per block; what one unit of the sweep in slot 3 needs is its caller's to say (`need3`).
+int32_t loop_budget(const phk_handle* h, int slot, int64_t need) {
+    static const int scale_of[4] = {0, 1, 2, 1};
+    const int s = scale_of[slot];
+    return (int32_t)std::min<int64_t>(2 * need * h->budget_num[s] / h->budget_den[s], INT32_MAX);
+}
+void set_budgets(const phk_handle* h, phk::KArgs* a, int T, int64_t need3) {
+    const int64_t nblk = (h->L + T - 1) / T, npieces = h->Lw / 4;
+    const int64_t need[4] = {npieces + 2 * (64 / T) + 8, nblk + 8, npieces + 16, need3};
+    for (int i = 0; i < 4; ++i) a->loop_budget[i] = loop_budget(h, i, need[i]);
+}
+// blocks of unit 0 of the segment sweep, the longest: every segment up to the one holding the warm-up boundary
+int64_t seg_unit_blocks(int T, int64_t W) {
+    const int64_t G = seg_blocks(T), segW = W > 0 ? ((W - 1) / T) / G : 0;
+    return G * (segW + 1);
+}
+
 // Enqueue one evaluation of `a` (ll, grad and scratch pointers set by the caller) under `plan`.
 // e_mid, if given, is recorded after the forward kernel.
 int enqueue(phk_handle* h, const Launchers& l, phk::KArgs a, const Plan& plan, bool want_grad, hipStream_t st,
@@ -458,17 +468,7 @@ int enqueue(phk_handle* h, const Launchers& l, phk::KArgs a, const Plan& plan, b
     const int64_t nseq = a.B * a.S;
     hipError_t e;
     a.seg_blocks = seg_blocks(plan.T);
-    {   // Iteration budgets (KArgs::loop_budget): twice what a healthy wave needs, from the row length alone.  The forward kernel
-        // and the beta scan make one outer iteration per 64-site piece (the ragged pieces at the warm-up boundary and the row's
-        // end a few more: one per block / word), a serial sweep one per block, a unit of the segment sweep one per block of its
-        // segments (unit 0: every segment up to the one holding the warm-up boundary).
-        const int64_t nblk = (h->L + plan.T - 1) / plan.T, npieces = h->Lw / 4, G = a.seg_blocks;
-        const int64_t segW = a.W > 0 ? ((a.W - 1) / plan.T) / G : 0;
-        const int64_t need[4] = {npieces + 2 * (64 / plan.T) + 8, nblk + 8, npieces + 16, G * (segW + 1) + 8};
-        const int scale_of[4] = {0, 1, 2, 1};
-        for (int i = 0; i < 4; ++i)
-            a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need[i] * h->budget_num[scale_of[i]] / h->budget_den[scale_of[i]], INT32_MAX);
-    }
+    set_budgets(h, &a, plan.T, seg_unit_blocks(plan.T, a.W) + 8);
     if (!want_grad) {
         e = l.fwd(plan.R1 && !plan.segmented ? plan.R1 : plan.R, plan.T, h->nrm, false, a, nt, st);
         if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, plan.R, plan.T, hipGetErrorString(e));
@@ -768,6 +768,189 @@ int autotune(phk_handle* h, const Launchers& l, const phk::KArgs& proto, bool wa
         std::fprintf(stderr, "phk tune: nseq %lld grad %d -> segmented %d R %d T %d R_forward %d R_scan %d hybrid_first %lld R_sweep %d\n", (long long)nseq,
                      (int)want_grad, best.segmented, best.R, best.T, best.R1, best.R2, (long long)best.hybrid_first, best.R3);
     h->tuned[{nseq, want_grad ? 1 : 0}] = best;
+    return PHK_OK;
+}
+
+// ---- One call over the (particle, chunk) grid: what phk_loglik and every sweep behind the forward pass share ----
+
+// what every such entry point gets from its caller
+struct CallShape {
+    const void* params;
+    int64_t pstride_b, pstride_s;
+    const float* prefold;
+    const int64_t* inds;
+    int64_t B, S, W;
+    double* ll;
+    void* stream;
+};
+
+// Cuts the grid into slabs of Bs particles x Ss chunks per launch sequence, so that the checkpoint store (sized for T = 8,
+// the densest spacing) and the `extra_bytes_per_seq` a sweep keeps beside it stay under the workspace limit, and sizes the
+// scratch for one slab.  With Ss < S a slab is one particle (Bs == 1): its rows of the outputs are contiguous.
+int slab_for(phk_handle* h, int64_t B, int64_t S, int64_t extra_bytes_per_seq, int64_t* Bs, int64_t* Ss) {
+    *Bs = B;
+    *Ss = S;
+    const int64_t per_seq = ((h->L + 7) / 8) * h->K * (int64_t)real_size(h) + extra_bytes_per_seq;
+    const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
+    if (B * S > max_seq) {
+        if (max_seq >= S) {
+            *Bs = max_seq / S;
+        } else {
+            *Bs = 1;
+            *Ss = max_seq;
+        }
+    }
+    return ensure_scratch(h, *Bs * *Ss);
+}
+
+// Kernel arguments of the slab of nb particles from b0 by ns chunks from s0, as a call without a gradient has them; a
+// caller sets what differs (ckpt / grad / part / asm_run for gradients, seg_blocks, the loop budgets).
+phk::KArgs base_kargs(const phk_handle* h, const CallShape& c, int64_t b0, int64_t nb, int64_t s0, int64_t ns) {
+    const size_t rs = real_size(h);
+    phk::KArgs a;
+    a.packed = h->packed;
+    a.Lw = h->Lw;
+    a.Ltot = h->L;
+    a.W = c.W;
+    a.inds = c.inds + s0;
+    a.params = (const char*)c.params + (size_t)(b0 * c.pstride_b + s0 * c.pstride_s) * rs;
+    a.pstride_b = c.pstride_b;
+    a.pstride_s = c.pstride_s;
+    a.B = nb;
+    a.S = ns;
+    a.ll = c.ll + b0 * c.S + s0;
+    a.ckpt = h->ckpt.p;
+    a.aux = (phk::SeqAux*)h->aux.p;
+    a.grad = nullptr;
+    a.gacc = (double*)h->gacc.p;
+    a.grad_dlog = 0;
+    a.eblk = (int16_t*)h->eblk.p;
+    a.eseg = (int32_t*)h->eseg.p;
+    a.seg_blocks = seg_blocks(8);
+    a.bseg = h->bseg.p;
+    a.fseg = (const int32_t*)h->fseg.p;
+    a.bpi = (double*)h->bpi.p;
+    a.risk = (int*)h->risk.p;
+    a.seq_begin = a.seq_end = 0;
+    a.N = h->N;
+    a.part = nullptr;
+    a.ops_f = a.ops_b = nullptr;  // slab_dense_ops sets them where the plan runs a one-state-per-lane kernel
+    for (int i = 0; i < 4; ++i) a.loop_budget[i] = INT32_MAX;
+    a.asm_run = 0;
+    a.scan_prio = 0;
+    a.mask_runs = h->mask_runs;
+    // the pre-folded blocks are laid out like the parameter blocks, five rows instead of seven
+    a.pfstride_b = c.pstride_b / 7 * 5;
+    a.pfstride_s = c.pstride_s / 7 * 5;
+    a.prefold = c.prefold ? c.prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
+    return a;
+}
+
+// The dense operator table: sized for a slab before anything of the call is enqueued (growing it later would synchronise the
+// device mid-step), then per slab built -- or, where the chunks share one block per particle, reused from the first chunk slab
+// of this particle range.
+int size_dense_ops(phk_handle* h, const CallShape& c, int64_t Bs, int64_t Ss) {
+    const int64_t blocks = Bs * (c.pstride_s != 0 ? Ss : 1);
+    return h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float));
+}
+int slab_dense_ops(phk_handle* h, phk::KArgs* a, int64_t s0, hipStream_t st) {
+    if (a->pstride_s != 0 || s0 == 0) return build_dense_ops(h, a, st);
+    a->ops_f = (const float*)h->ops.p;
+    a->ops_b = a->ops_f + a->B * phk::DENSE_OPS_FLOATS;
+    return PHK_OK;
+}
+
+int check_prefold(const phk_handle* h, const float* prefold, int64_t pstride_b, int64_t pstride_s) {
+    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    return PHK_OK;
+}
+
+// The plan a gradient call of this slab shape would run, and its forward leg's variant Rf.  The plan is read, never tuned or
+// recorded: a sweep leaves the autotune cache and everything a gradient call decides unchanged.
+int read_plan(const phk_handle* h, int64_t Bs, int64_t Ss, int64_t W, Plan* plan, int* Rf) {
+    *plan = adjust_hybrid(h, choose_plan(h, Bs * Ss, W, 1), Bs);
+    *Rf = plan->segmented ? plan->R1 : (plan->R1 ? plan->R1 : plan->R);
+    if (!valid_Rf(h, *Rf) || !valid_T(h->K, *Rf, plan->T)) return fail(PHK_EINVAL, "forward variant R=%d T=%d not available for K=%d", *Rf, plan->T, h->K);
+    return PHK_OK;
+}
+
+// One sweep behind the forward pass: what its entry point hands to run_sweep.  The callbacks are the entry point's lambdas.
+template <typename Validate, typename Prepare, typename Launch>
+struct Sweep {
+    const char* name;             // in launch errors
+    Validate validate;            // int(): the sweep's own argument checks, PHK_OK or fail(...)
+    int64_t extra_bytes_per_seq;  // workspace per sequence beside the checkpoint store (pair counts)
+    Prepare prepare;              // int(units, nseq): sizes that workspace before anything is enqueued
+    Launch launch;                // hipError_t(T, nrm, kargs, b0, s0, units, stream): its own arguments for the slab at (b0, s0), its launcher
+    Sweep(const char* n, Validate v, int64_t x, Prepare p, Launch l) : name(n), validate(v), extra_bytes_per_seq(x), prepare(p), launch(l) {}
+};
+const auto no_workspace = [](int, int64_t) { return (int)PHK_OK; };
+
+// The forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient call of this shape would run,
+// then `sw` in the gradient sweep's place, per slab of the checkpoint store.  A hybrid plan runs as its serial half.
+template <typename S>
+int run_sweep(phk_handle* h, const CallShape& c, int bin, const S& sw) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
+    if (c.W < 0 || c.W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)c.W, (long long)h->L);
+    // (W = L: no scored site, nbin = 0, ll = 0 -- the outputs are empty, and an empty device buffer may well be a null pointer)
+    if (int rc = sw.validate(); rc != PHK_OK) return rc;
+    if (!c.params || !c.inds || !c.ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
+    if (c.B < 0 || c.S < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");
+    if (int rc = check_prefold(h, c.prefold, c.pstride_b, c.pstride_s); rc != PHK_OK) return rc;
+    if (c.B == 0 || c.S == 0) return PHK_OK;
+    Launchers l;
+    if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)c.stream;
+    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
+    const int K = h->K;
+
+    int64_t Bs, Ss;
+    if (int rc = slab_for(h, c.B, c.S, sw.extra_bytes_per_seq, &Bs, &Ss); rc != PHK_OK) return rc;
+    Plan plan;
+    int Rf;
+    if (int rc = read_plan(h, Bs, Ss, c.W, &plan, &Rf); rc != PHK_OK) return rc;
+    if (plan.segmented && !valid_Rf(h, plan.R2)) return fail(PHK_EINVAL, "beta-scan variant R=%d not available for K=%d", plan.R2, K);
+    const bool dense = dense_capable(h) && (Rf == 16 || (plan.segmented && plan.R2 == 16));
+    if (dense) {
+        if (int rc = size_dense_ops(h, c, Bs, Ss); rc != PHK_OK) return rc;
+    }
+    const int units = plan.segmented ? (int)n_units(h, plan.T, c.W) : 0;
+    if (int rc = sw.prepare(units, Bs * Ss); rc != PHK_OK) return rc;
+
+    for (int64_t b0 = 0; b0 < c.B; b0 += Bs) {
+        const int64_t nb = std::min(Bs, c.B - b0);
+        for (int64_t s0 = 0; s0 < c.S; s0 += Ss) {
+            const int64_t ns = std::min(Ss, c.S - s0);
+            phk::KArgs a = base_kargs(h, c, b0, nb, s0, ns);
+            a.seg_blocks = seg_blocks(plan.T);
+            set_budgets(h, &a, plan.T, seg_unit_blocks(plan.T, c.W) + bin / plan.T + 8);  // (a unit may walk up to one bin past its left edge)
+            if (dense) {
+                if (int rc = slab_dense_ops(h, &a, s0, st); rc != PHK_OK) return rc;
+            }
+            hipError_t e;
+            if (!plan.segmented) {
+                e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+                e = sw.launch(plan.T, h->nrm, a, b0, s0, 0, st);
+                if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", sw.name, K, plan.T, hipGetErrorString(e));
+                continue;
+            }
+            // segmented: forward kernel || beta scan (second stream), then the sweep's units
+            HIP_TRY(hipEventRecord(h->ev_fork, st));
+            HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
+            e = l.fwd(Rf, plan.T, h->nrm, true, a, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+            e = l.bscan(plan.R2, h->nrm, a, (int64_t)SEG_SITES, h->bseg.p, (int32_t*)h->fseg.p, 256, h->side);
+            if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
+            HIP_TRY(hipEventRecord(h->ev_join, h->side));
+            HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
+            e = sw.launch(plan.T, h->nrm, a, b0, s0, units, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", sw.name, K, plan.T, units, hipGetErrorString(e));
+        }
+    }
     return PHK_OK;
 }
 
@@ -1383,121 +1566,72 @@ int phk_prefold(int device, int K, const double* params, int64_t nblocks, float*
     return PHK_OK;
 }
 
-static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
-                       const int64_t* inds, int64_t B, int64_t S, int64_t W, double* ll, void* grad, int grad_dlog, void* stream);
+static int loglik_impl(phk_handle* h, const CallShape& c, void* grad, int grad_dlog);
 
 int phk_loglik(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const int64_t* inds,
                int64_t B, int64_t S, int64_t W, double* ll, void* grad, int grad_dlog, void* stream) {
-    return loglik_impl(h, params, pstride_b, pstride_s, nullptr, inds, B, S, W, ll, grad, grad_dlog, stream);
+    return loglik_impl(h, {params, pstride_b, pstride_s, nullptr, inds, B, S, W, ll, stream}, grad, grad_dlog);
 }
 
 int phk_loglik_prefolded(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                          const int64_t* inds, int64_t B, int64_t S, int64_t W, double* ll, void* grad, int grad_dlog, void* stream) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
     if (!prefold) return fail(PHK_EINVAL, "prefold is NULL (phk_loglik takes blocks without pre-folded factors)");
-    if (h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
-    if (pstride_b % 7 != 0 || pstride_s % 7 != 0) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
-    return loglik_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, grad, grad_dlog, stream);
+    if (int rc = check_prefold(h, prefold, pstride_b, pstride_s); rc != PHK_OK) return rc;
+    return loglik_impl(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, grad, grad_dlog);
 }
 
-static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
-                       const int64_t* inds, int64_t B, int64_t S, int64_t W, double* ll, void* grad, int grad_dlog, void* stream) {
+static int loglik_impl(phk_handle* h, const CallShape& c, void* grad, int grad_dlog) {
+    const int64_t B = c.B, S = c.S, W = c.W;
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
-    if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
+    if (!c.params || !c.inds || !c.ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
     if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
     if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
     if (B == 0 || S == 0) return PHK_OK;
     Launchers l;
     if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
     HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
+    hipStream_t st = (hipStream_t)c.stream;
     h->last_stream = st;
-    const size_t rs = real_size(h);
     const int K = h->K;
     const bool want_grad = grad != nullptr;
     h->n_last = 0;
     if (h->n_launches > 4096) h->n_launches = 0;  // nobody is collecting: recycle the event pool
 
-    // slab the (particle, chunk) grid so that the checkpoint store (sized for T = 8, the densest
-    // spacing) stays under the workspace limit
-    int64_t Bs = B, Ss = S;
+    int64_t Bs = B, Ss = S;  // (no gradient: no checkpoint store, one slab)
     if (want_grad) {
-        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
-        int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
-        if (B * S > max_seq) {
-            if (max_seq >= S) {
-                Bs = max_seq / S;
-            } else {
-                Bs = 1;
-                Ss = max_seq;
-            }
-        }
-        int rc = ensure_scratch(h, Bs * Ss);
-        if (rc != PHK_OK) return rc;
+        if (int rc = slab_for(h, B, S, 0, &Bs, &Ss); rc != PHK_OK) return rc;
     }
-
     auto make_args = [&](int64_t b0, int64_t nb, int64_t s0, int64_t ns) {
-        phk::KArgs a;
-        a.packed = h->packed;
-        a.Lw = h->Lw;
-        a.Ltot = h->L;
-        a.W = W;
-        a.inds = inds + s0;
-        a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
-        a.pstride_b = pstride_b;
-        a.pstride_s = pstride_s;
-        a.B = nb;
-        a.S = ns;
-        // with Ss < S the slab is one particle (nb == 1): rows b0*S + s0 .. are contiguous
-        a.ll = ll + b0 * S + s0;
+        phk::KArgs a = base_kargs(h, c, b0, nb, s0, ns);  // (enqueue() sets the plan's seg_blocks, loop budgets and scan_prio)
         a.ckpt = want_grad ? h->ckpt.p : nullptr;
-        a.aux = (phk::SeqAux*)h->aux.p;
-        a.grad = want_grad ? (char*)grad + (size_t)(b0 * S + s0) * 7 * K * rs : nullptr;
-        a.gacc = (double*)h->gacc.p;
+        a.grad = want_grad ? (char*)grad + (size_t)(b0 * S + s0) * 7 * K * real_size(h) : nullptr;
         a.grad_dlog = grad_dlog;
-        a.eblk = (int16_t*)h->eblk.p;
-        a.eseg = (int32_t*)h->eseg.p;
-        a.seg_blocks = seg_blocks(8);  // enqueue() sets the plan's value
-        a.bseg = h->bseg.p;
-        a.fseg = (const int32_t*)h->fseg.p;
-        a.bpi = (double*)h->bpi.p;
-        a.risk = (int*)h->risk.p;
-        a.seq_begin = a.seq_end = 0;
-        a.N = h->N;
         a.part = h->part.p;
-        a.ops_f = a.ops_b = nullptr;  // build_dense_ops sets them where the plan runs a one-state-per-lane kernel
-        // the pre-folded blocks are laid out like the parameter blocks, five rows instead of seven
-        for (int i = 0; i < 4; ++i) a.loop_budget[i] = INT32_MAX;  // enqueue() sets the plan's values
         a.asm_run = h->asm_run;
-        a.scan_prio = 0;  // enqueue() sets the plan's value
-        a.mask_runs = h->mask_runs;
-        a.pfstride_b = pstride_b / 7 * 5;
-        a.pfstride_s = pstride_s / 7 * 5;
-        a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
         return a;
     };
 
     // plan for this launch shape: forced, tuned earlier, tuned now, or the static rule
-    const int64_t nseq_launch = std::min(Bs, B) * std::min(Ss, S);
+    const int64_t nseq_launch = Bs * Ss;
     if (h->autotune && !h->deterministic && !h->has_forced_plan && !h->force_R && !h->force_T && h->mode < 0 && h->L >= 512 && nseq_launch >= 64 &&
         !h->tuned.count({nseq_launch, want_grad ? 1 : 0})) {
-        int rc = autotune(h, l, make_args(0, std::min(Bs, B), 0, std::min(Ss, S)), want_grad, st);
+        int rc = autotune(h, l, make_args(0, Bs, 0, Ss), want_grad, st);
         if (rc != PHK_OK) return rc;
     }
-    const Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, want_grad ? 1 : 0), std::min(Bs, B));
+    const Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, want_grad ? 1 : 0), Bs);
     if (!(want_grad ? (plan.segmented ? valid_Rs(h, plan.R) : valid_Rb(h, plan.R)) : valid_Rf(h, plan.R)) || !valid_T(K, plan.R, plan.T))
         return fail(PHK_EINVAL, "R=%d T=%d not available for K=%d", plan.R, plan.T, K);
     if (want_grad && !plan.segmented && plan.hybrid_first > 0 && !valid_Rs(h, plan.R3)) return fail(PHK_EINVAL, "segment sweep R=%d not available for K=%d", plan.R3, K);
     if (plan.segmented && (!valid_Rf(h, plan.R1) || !valid_Rf(h, plan.R2))) return fail(PHK_EINVAL, "invalid segmented plan for K=%d", K);
     if (!plan.segmented && plan.R1 != 0 && !valid_Rf(h, plan.R1)) return fail(PHK_EINVAL, "forward variant R=%d not available for K=%d", plan.R1, K);
-    if (plan_uses_dense(h, plan)) {  // sized before anything of this call is enqueued (growing it later would synchronise the device mid-step)
-        const int64_t blocks = std::min(Bs, B) * (pstride_s != 0 ? std::min(Ss, S) : 1);
-        if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
+    if (plan_uses_dense(h, plan)) {
+        if (int rc = size_dense_ops(h, c, Bs, Ss); rc != PHK_OK) return rc;
     }
     h->last_total = B * S;
     h->last_plan = plan;
-    h->last_Bs = std::min(Bs, B);
-    h->last_Ss = std::min(Ss, S);
+    h->last_Bs = Bs;
+    h->last_Ss = Ss;
 
     for (int64_t b0 = 0; b0 < B; b0 += Bs) {
         const int64_t nb = std::min(Bs, B - b0);
@@ -1505,12 +1639,7 @@ static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int
             const int64_t ns = std::min(Ss, S - s0);
             phk::KArgs a = make_args(b0, nb, s0, ns);
             if (plan_uses_dense(h, plan)) {
-                if (pstride_s == 0 && s0 > 0) {  // one block per particle: the table of this particle range is built already
-                    a.ops_f = (const float*)h->ops.p;
-                    a.ops_b = a.ops_f + nb * phk::DENSE_OPS_FLOATS;
-                } else if (int rc = build_dense_ops(h, &a, st); rc != PHK_OK) {
-                    return rc;
-                }
+                if (int rc = slab_dense_ops(h, &a, s0, st); rc != PHK_OK) return rc;
             }
             if (h->poison) {
                 // diagnostic (environment PHK_POISON=<byte>, e.g. 255 = NaN patterns): fill every scratch buffer with that byte before every
@@ -1548,310 +1677,145 @@ static int loglik_impl(phk_handle* h, const void* params, int64_t pstride_b, int
     return PHK_OK;
 }
 
-// what phk_transitions hands to posterior_impl in place of mean / marginals
-struct TransOut {
-    const int64_t* lens;
-    void* arrivals;
-    void* changes;
-    void* track;  // phk_predictive: the predictive sweep (launch_loo.hip) runs instead, arrivals and changes are unused
-    bool loo;
-    const double* weights;  // phk_tracts: the tract sweep (launch_tract.hip) runs instead, with these weights [B, K] / [K] ...
-    int64_t wstride_b;
-    void* tract;  // ... into this output
-    bool tracts;
-    // phk_local_ratio: the local-ratio sweep (launch_local.hip) runs instead, with these alternative blocks (laid out like params) ...
-    const void* alt;
-    int64_t astride_b, astride_s;
-    const float* alt_prefold;
-    void* logratio;  // ... into this output
-    bool local;
-    // phk_pair_counts: the pair-count sweep (launch_pairs.hip) runs instead, into this output (double [B, S, K, K])
-    double* counts;
-    bool pairs;
-};
-
-// Posterior decoding (phk_posterior): the forward leg -- and, for a segmented plan, the beta-scan leg -- of the plan a gradient
-// call of this shape would run, then the decode sweep instead of the gradient sweep.  The plan is read, never tuned or recorded:
-// decoding leaves the autotune cache and everything a gradient call decides unchanged.
-// tr != nullptr (phk_transitions): the same legs, slabs and stream ordering with the transition sweep (launch_trans.hip) in the
-// decode sweep's place; values, mean and marginals are unused then.  tr->loo (phk_predictive): the leave-one-out predictive sweep
-// (launch_loo.hip) in that place.  tr->tracts (phk_tracts): the tract-posterior sweep (launch_tract.hip) in that place.  tr->local
-// (phk_local_ratio): the local likelihood-ratio sweep (launch_local.hip) in that place.  tr->pairs (phk_pair_counts): the pair-count
-// sweep (launch_pairs.hip) in that place, at bin = 1; its per-unit float64 partials are workspace of the call and part of the slab
-// arithmetic.
-static int posterior_impl(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
-                          const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
-                          double* ll, void* mean, void* marginals, void* stream, const TransOut* tr = nullptr) {
-    if (!h) return fail(PHK_EINVAL, "handle is NULL");
-    if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
-    if (W < 0 || W > h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld]", (long long)W, (long long)h->L);
-    // (W = L: no scored site, nbin = 0, ll = 0 -- the outputs are empty, and an empty device buffer may well be a null pointer)
-    if (tr && tr->loo && !tr->track && W < h->L) return fail(PHK_EINVAL, "track is NULL: nothing to compute");
-    if (tr && tr->tracts && !tr->weights) return fail(PHK_EINVAL, "weights must be a non-NULL device pointer (double [B, K] or [K])");
-    if (tr && tr->tracts && tr->wstride_b < 0) return fail(PHK_EINVAL, "wstride_b must be >= 0");
-    if (tr && tr->tracts && !tr->tract && W < h->L) return fail(PHK_EINVAL, "tract is NULL: nothing to compute");
-    if (tr && tr->local && !tr->alt) return fail(PHK_EINVAL, "alt_params must be a non-NULL device pointer (blocks laid out like params)");
-    if (tr && tr->local && (tr->astride_b < 0 || tr->astride_s < 0)) return fail(PHK_EINVAL, "astride_b and astride_s must be >= 0");
-    if (tr && tr->local && !tr->logratio && W < h->L) return fail(PHK_EINVAL, "logratio is NULL: nothing to compute");
-    if (tr && tr->local && tr->alt_prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
-    if (tr && tr->local && tr->alt_prefold && (tr->astride_b % 7 != 0 || tr->astride_s % 7 != 0)) return fail(PHK_EINVAL, "alternative strides must be multiples of 7 (whole [7, K] blocks)");
-    if (tr && tr->pairs && !tr->counts && W < h->L) return fail(PHK_EINVAL, "counts is NULL: nothing to compute");
-    if (tr && !tr->loo && !tr->tracts && !tr->local && !tr->pairs && !tr->arrivals && !tr->changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
-    if (!tr && !mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
-    if (!params || !inds || !ll) return fail(PHK_EINVAL, "params, inds and ll must be non-NULL device pointers");
-    if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
-    if (B < 0 || S < 0 || vstride_b < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");
-    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
-    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
-    if (B == 0 || S == 0) return PHK_OK;
-    Launchers l;
-    if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
-    typedef hipError_t (*dec_fn)(int, int, const phk::KArgs&, const phk::DArgs&, int, int, hipStream_t);
-    dec_fn dec = nullptr;
-#define PHK_CASE(k) \
-    case k: dec = h->dbl ? phk::launch_decode_f64_##k : phk::launch_decode_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    typedef hipError_t (*trn_fn)(int, int, const phk::KArgs&, const phk::TArgs&, int, int, hipStream_t);
-    trn_fn trn = nullptr;
-#define PHK_CASE(k) \
-    case k: trn = h->dbl ? phk::launch_trans_f64_##k : phk::launch_trans_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    typedef hipError_t (*loo_fn)(int, int, const phk::KArgs&, const phk::LArgs&, int, int, hipStream_t);
-    loo_fn loo = nullptr;
-#define PHK_CASE(k) \
-    case k: loo = h->dbl ? phk::launch_loo_f64_##k : phk::launch_loo_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    typedef hipError_t (*trc_fn)(int, int, const phk::KArgs&, const phk::QArgs&, int, int, hipStream_t);
-    trc_fn trc = nullptr;
-#define PHK_CASE(k) \
-    case k: trc = h->dbl ? phk::launch_tract_f64_##k : phk::launch_tract_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    typedef hipError_t (*lcl_fn)(int, int, const phk::KArgs&, const phk::RArgs&, int, int, hipStream_t);
-    lcl_fn lcl = nullptr;
-#define PHK_CASE(k) \
-    case k: lcl = h->dbl ? phk::launch_local_f64_##k : phk::launch_local_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    typedef hipError_t (*prs_fn)(int, int, const phk::KArgs&, const phk::PArgs&, int, int, hipStream_t);
-    prs_fn prs = nullptr;
-#define PHK_CASE(k) \
-    case k: prs = h->dbl ? phk::launch_pairs_f64_##k : phk::launch_pairs_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    const bool is_prs = tr && tr->pairs;
-    const bool is_loo = tr && tr->loo;
-    const bool is_trc = tr && tr->tracts;
-    const bool is_lcl = tr && tr->local;
-    const char* const sweep_name = is_prs ? "pair-count" : is_lcl ? "local-ratio" : is_trc ? "tract" : is_loo ? "predictive" : (tr ? "transition" : "decode");
-    HIP_TRY(hipSetDevice(h->device));
-    hipStream_t st = (hipStream_t)stream;
-    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
-    const size_t rs = real_size(h);
-    const int K = h->K;
-    const int64_t nbin = (h->L - W + bin - 1) / bin;
-
-    // the checkpoint store is slabbed as for a gradient call
-    int64_t Bs = B, Ss = S;
-    {
-        // (pair counts: plus a [K, K] float64 partial per unit and sequence, sized for the plan with the most units -- the plan
-        // is chosen by the slab, so the slab cannot wait for it)
-        const int64_t units_max = std::max<int64_t>(1, std::max(n_units(h, 8, W), n_units(h, 16, W)));
-        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs + (is_prs ? units_max * K * K * (int64_t)sizeof(double) : 0);
-        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
-        if (B * S > max_seq) {
-            if (max_seq >= S) {
-                Bs = max_seq / S;
-            } else {
-                Bs = 1;
-                Ss = max_seq;
-            }
-        }
-        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
-    }
-    const int64_t nseq_launch = std::min(Bs, B) * std::min(Ss, S);
-    Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, 1), std::min(Bs, B));
-    const int Rf = plan.segmented ? plan.R1 : (plan.R1 ? plan.R1 : plan.R);  // the forward leg's variant
-    plan.hybrid_first = 0;  // a hybrid plan runs as its serial half
-    if (!valid_Rf(h, Rf) || !valid_T(K, Rf, plan.T)) return fail(PHK_EINVAL, "forward variant R=%d T=%d not available for K=%d", Rf, plan.T, K);
-    if (plan.segmented && !valid_Rf(h, plan.R2)) return fail(PHK_EINVAL, "beta-scan variant R=%d not available for K=%d", plan.R2, K);
-    const bool dense = dense_capable(h) && (Rf == 16 || (plan.segmented && plan.R2 == 16));
-    if (dense) {
-        const int64_t blocks = std::min(Bs, B) * (pstride_s != 0 ? std::min(Ss, S) : 1);
-        if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
-    }
-    const int units = plan.segmented ? (int)n_units(h, plan.T, W) : 0;
-    if (is_prs) {  // sized before anything of this call is enqueued
-        if (int rc = h->pairs.ensure((size_t)std::max(units, 1) * (size_t)nseq_launch * K * K * sizeof(double)); rc != PHK_OK) return rc;
-    }
-
-    for (int64_t b0 = 0; b0 < B; b0 += Bs) {
-        const int64_t nb = std::min(Bs, B - b0);
-        for (int64_t s0 = 0; s0 < S; s0 += Ss) {
-            const int64_t ns = std::min(Ss, S - s0);
-            phk::KArgs a;
-            a.packed = h->packed;
-            a.Lw = h->Lw;
-            a.Ltot = h->L;
-            a.W = W;
-            a.inds = inds + s0;
-            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
-            a.pstride_b = pstride_b;
-            a.pstride_s = pstride_s;
-            a.B = nb;
-            a.S = ns;
-            a.ll = ll + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
-            a.ckpt = h->ckpt.p;
-            a.aux = (phk::SeqAux*)h->aux.p;
-            a.grad = nullptr;
-            a.gacc = (double*)h->gacc.p;
-            a.grad_dlog = 0;
-            a.eblk = (int16_t*)h->eblk.p;
-            a.eseg = (int32_t*)h->eseg.p;
-            a.seg_blocks = seg_blocks(plan.T);
-            a.bseg = h->bseg.p;
-            a.fseg = (const int32_t*)h->fseg.p;
-            a.bpi = (double*)h->bpi.p;
-            a.risk = (int*)h->risk.p;
-            a.seq_begin = a.seq_end = 0;
-            a.N = h->N;
-            a.part = nullptr;
-            a.ops_f = a.ops_b = nullptr;
-            a.asm_run = 0;
-            a.scan_prio = 0;
-            a.mask_runs = h->mask_runs;
-            a.pfstride_b = pstride_b / 7 * 5;
-            a.pfstride_s = pstride_s / 7 * 5;
-            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
-            {   // iteration budgets, twice what a healthy wave needs (see enqueue); a decode unit may walk up to one bin past its left edge
-                const int64_t nblk = (h->L + plan.T - 1) / plan.T, npieces = h->Lw / 4, G = a.seg_blocks;
-                const int64_t segW = W > 0 ? ((W - 1) / plan.T) / G : 0;
-                const int64_t need[4] = {npieces + 2 * (64 / plan.T) + 8, nblk + 8, npieces + 16, G * (segW + 1) + bin / plan.T + 8};
-                const int scale_of[4] = {0, 1, 2, 1};
-                for (int i = 0; i < 4; ++i)
-                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need[i] * h->budget_num[scale_of[i]] / h->budget_den[scale_of[i]], INT32_MAX);
-            }
-            if (dense) {
-                if (pstride_s == 0 && s0 > 0) {
-                    a.ops_f = (const float*)h->ops.p;
-                    a.ops_b = a.ops_f + nb * phk::DENSE_OPS_FLOATS;
-                } else if (int rc = build_dense_ops(h, &a, st); rc != PHK_OK) {
-                    return rc;
-                }
-            }
-            phk::DArgs d;
-            d.bin = bin;
-            d.nbin = nbin;
-            d.values = values ? values + b0 * vstride_b : nullptr;
-            d.vstride_b = vstride_b;
-            d.mean = mean ? (char*)mean + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
-            d.marg = marginals ? (char*)marginals + (size_t)((b0 * S + s0) * nbin * K) * rs : nullptr;
-            phk::TArgs t;
-            t.bin = bin;
-            t.nbin = nbin;
-            t.lens = tr ? tr->lens : nullptr;
-            t.arr = tr && tr->arrivals ? (char*)tr->arrivals + (size_t)((b0 * S + s0) * nbin * 3 * K) * rs : nullptr;
-            t.chg = tr && tr->changes ? (char*)tr->changes + (size_t)((b0 * S + s0) * nbin * 2) * rs : nullptr;
-            phk::LArgs lo;
-            lo.bin = bin;
-            lo.nbin = nbin;
-            lo.lens = tr ? tr->lens : nullptr;
-            lo.track = is_loo && tr->track ? (char*)tr->track + (size_t)((b0 * S + s0) * nbin * 3) * rs : nullptr;
-            phk::QArgs qa;
-            qa.bin = bin;
-            qa.nbin = nbin;
-            qa.lens = tr ? tr->lens : nullptr;
-            qa.weights = is_trc ? tr->weights + b0 * tr->wstride_b : nullptr;
-            qa.wstride_b = is_trc ? tr->wstride_b : 0;
-            qa.tract = is_trc && tr->tract ? (char*)tr->tract + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
-            phk::RArgs ra;
-            ra.bin = bin;
-            ra.nbin = nbin;
-            ra.lens = tr ? tr->lens : nullptr;
-            ra.alt = is_lcl ? (const char*)tr->alt + (size_t)(b0 * tr->astride_b + s0 * tr->astride_s) * rs : nullptr;
-            ra.astride_b = is_lcl ? tr->astride_b : 0;
-            ra.astride_s = is_lcl ? tr->astride_s : 0;
-            ra.apfstride_b = ra.astride_b / 7 * 5;  // laid out like the alternative blocks, five rows instead of seven
-            ra.apfstride_s = ra.astride_s / 7 * 5;
-            ra.alt_prefold = is_lcl && tr->alt_prefold ? tr->alt_prefold + (b0 * ra.apfstride_b + s0 * ra.apfstride_s) : nullptr;
-            ra.logratio = is_lcl && tr->logratio ? (char*)tr->logratio + (size_t)((b0 * S + s0) * nbin) * rs : nullptr;
-            phk::PArgs pa;
-            pa.lens = tr ? tr->lens : nullptr;
-            pa.part = (double*)h->pairs.p;
-            pa.counts = is_prs && tr->counts ? tr->counts + (b0 * S + s0) * K * K : nullptr;
-            pa.row0 = 0;
-            hipError_t e;
-            if (!plan.segmented) {
-                e = l.fwd(Rf, plan.T, h->nrm, true, a, FWD_NT, st);
-                if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-                e = is_prs ? prs(plan.T, h->nrm, a, pa, 0, 256, st) : is_lcl ? lcl(plan.T, h->nrm, a, ra, 0, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, 0, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, 0, 256, st) : tr ? trn(plan.T, h->nrm, a, t, 0, 256, st) : dec(plan.T, h->nrm, a, d, 0, 256, st);
-                if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d): %s", sweep_name, K, plan.T, hipGetErrorString(e));
-                continue;
-            }
-            // segmented: forward kernel || beta scan (second stream), then the decode units
-            HIP_TRY(hipEventRecord(h->ev_fork, st));
-            HIP_TRY(hipStreamWaitEvent(h->side, h->ev_fork, 0));
-            e = l.fwd(Rf, plan.T, h->nrm, true, a, 256, st);
-            if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
-            e = l.bscan(plan.R2, h->nrm, a, (int64_t)SEG_SITES, h->bseg.p, (int32_t*)h->fseg.p, 256, h->side);
-            if (e != hipSuccess) return fail(PHK_EHIP, "beta-scan kernel launch (K=%d R=%d): %s", K, plan.R2, hipGetErrorString(e));
-            HIP_TRY(hipEventRecord(h->ev_join, h->side));
-            HIP_TRY(hipStreamWaitEvent(st, h->ev_join, 0));
-            e = is_prs ? prs(plan.T, h->nrm, a, pa, units, 256, st) : is_lcl ? lcl(plan.T, h->nrm, a, ra, units, 256, st) : is_trc ? trc(plan.T, h->nrm, a, qa, units, 256, st) : is_loo ? loo(plan.T, h->nrm, a, lo, units, 256, st) : tr ? trn(plan.T, h->nrm, a, t, units, 256, st) : dec(plan.T, h->nrm, a, d, units, 256, st);
-            if (e != hipSuccess) return fail(PHK_EHIP, "%s kernel launch (K=%d T=%d units=%d): %s", sweep_name, K, plan.T, units, hipGetErrorString(e));
-        }
-    }
-    return PHK_OK;
-}
+// The six sweeps that run_sweep runs in the gradient sweep's place.  Each entry point states its own argument checks, its own
+// argument struct for the slab at (b0, s0) of the call's [B, S] outputs, and its launcher.
 
 int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                   const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
                   double* ll, void* mean, void* marginals, void* stream) {
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, values, vstride_b, ll, mean, marginals, stream);
+    const auto validate = [&] {
+        if (!mean && !marginals && W < h->L) return fail(PHK_EINVAL, "mean and marginals are both NULL: nothing to decode");
+        if (mean && !values) return fail(PHK_EINVAL, "mean needs values (device double [B, K] or [K])");
+        if (vstride_b < 0) return fail(PHK_EINVAL, "B, S and vstride_b must be >= 0");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        const size_t rs = real_size(h);
+        phk::DArgs d;
+        d.bin = bin;
+        d.nbin = (h->L - W + bin - 1) / bin;
+        d.values = values ? values + b0 * vstride_b : nullptr;
+        d.vstride_b = vstride_b;
+        d.mean = mean ? (char*)mean + (size_t)((b0 * S + s0) * d.nbin) * rs : nullptr;
+        d.marg = marginals ? (char*)marginals + (size_t)((b0 * S + s0) * d.nbin * h->K) * rs : nullptr;
+        return PHK_PICK(decode, h)(T, nrm, a, d, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("decode", validate, 0, no_workspace, launch));
 }
 
 int phk_transitions(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* arrivals,
                     void* changes, void* stream) {
-    const TransOut tr = {lens, arrivals, changes, nullptr, false};
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+    const auto validate = [&] {
+        if (!arrivals && !changes && W < h->L) return fail(PHK_EINVAL, "arrivals and changes are both NULL: nothing to compute");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        const size_t rs = real_size(h);
+        phk::TArgs t;
+        t.bin = bin;
+        t.nbin = (h->L - W + bin - 1) / bin;
+        t.lens = lens;
+        t.arr = arrivals ? (char*)arrivals + (size_t)((b0 * S + s0) * t.nbin * 3 * h->K) * rs : nullptr;
+        t.chg = changes ? (char*)changes + (size_t)((b0 * S + s0) * t.nbin * 2) * rs : nullptr;
+        return PHK_PICK(trans, h)(T, nrm, a, t, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("transition", validate, 0, no_workspace, launch));
 }
 
 int phk_predictive(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* track,
                    void* stream) {
-    const TransOut tr = {lens, nullptr, nullptr, track, true};
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+    const auto validate = [&] {
+        if (!track && W < h->L) return fail(PHK_EINVAL, "track is NULL: nothing to compute");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        phk::LArgs lo;
+        lo.bin = bin;
+        lo.nbin = (h->L - W + bin - 1) / bin;
+        lo.lens = lens;
+        lo.track = track ? (char*)track + (size_t)((b0 * S + s0) * lo.nbin * 3) * real_size(h) : nullptr;
+        return PHK_PICK(loo, h)(T, nrm, a, lo, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("predictive", validate, 0, no_workspace, launch));
 }
 
 int phk_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
                int64_t B, int64_t S, int64_t W, int bin, const double* weights, int64_t wstride_b, const int64_t* lens, double* ll,
                void* tract, void* stream) {
-    const TransOut tr = {lens, nullptr, nullptr, nullptr, false, weights, wstride_b, tract, true};
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+    const auto validate = [&] {
+        if (!weights) return fail(PHK_EINVAL, "weights must be a non-NULL device pointer (double [B, K] or [K])");
+        if (wstride_b < 0) return fail(PHK_EINVAL, "wstride_b must be >= 0");
+        if (!tract && W < h->L) return fail(PHK_EINVAL, "tract is NULL: nothing to compute");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        phk::QArgs qa;
+        qa.bin = bin;
+        qa.nbin = (h->L - W + bin - 1) / bin;
+        qa.lens = lens;
+        qa.weights = weights + b0 * wstride_b;
+        qa.wstride_b = wstride_b;
+        qa.tract = tract ? (char*)tract + (size_t)((b0 * S + s0) * qa.nbin) * real_size(h) : nullptr;
+        return PHK_PICK(tract, h)(T, nrm, a, qa, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("tract", validate, 0, no_workspace, launch));
 }
 
 int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                     const void* alt_params, int64_t astride_b, int64_t astride_s, const float* alt_prefold, const int64_t* inds,
                     int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens, double* ll, void* logratio, void* stream) {
-    const TransOut tr = {lens, nullptr, nullptr, nullptr, false, nullptr, 0, nullptr, false, alt_params, astride_b, astride_s, alt_prefold, logratio, true};
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, bin, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+    const auto validate = [&] {
+        if (!alt_params) return fail(PHK_EINVAL, "alt_params must be a non-NULL device pointer (blocks laid out like params)");
+        if (astride_b < 0 || astride_s < 0) return fail(PHK_EINVAL, "astride_b and astride_s must be >= 0");
+        if (!logratio && W < h->L) return fail(PHK_EINVAL, "logratio is NULL: nothing to compute");
+        if (alt_prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
+        if (alt_prefold && (astride_b % 7 != 0 || astride_s % 7 != 0)) return fail(PHK_EINVAL, "alternative strides must be multiples of 7 (whole [7, K] blocks)");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        const size_t rs = real_size(h);
+        phk::RArgs ra;
+        ra.bin = bin;
+        ra.nbin = (h->L - W + bin - 1) / bin;
+        ra.lens = lens;
+        ra.alt = (const char*)alt_params + (size_t)(b0 * astride_b + s0 * astride_s) * rs;
+        ra.astride_b = astride_b;
+        ra.astride_s = astride_s;
+        ra.apfstride_b = astride_b / 7 * 5;  // laid out like the alternative blocks, five rows instead of seven
+        ra.apfstride_s = astride_s / 7 * 5;
+        ra.alt_prefold = alt_prefold ? alt_prefold + (b0 * ra.apfstride_b + s0 * ra.apfstride_s) : nullptr;
+        ra.logratio = logratio ? (char*)logratio + (size_t)((b0 * S + s0) * ra.nbin) * rs : nullptr;
+        return PHK_PICK(local, h)(T, nrm, a, ra, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("local-ratio", validate, 0, no_workspace, launch));
 }
 
 int phk_pair_counts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, const int64_t* lens, double* ll, double* counts, void* stream) {
-    TransOut tr = {};
-    tr.lens = lens;
-    tr.counts = counts;
-    tr.pairs = true;
-    return posterior_impl(h, params, pstride_b, pstride_s, prefold, inds, B, S, W, 1, nullptr, 0, ll, nullptr, nullptr, stream, &tr);
+    const auto validate = [&] {
+        if (!counts && W < h->L) return fail(PHK_EINVAL, "counts is NULL: nothing to compute");
+        return (int)PHK_OK;
+    };
+    // a [K, K] float64 partial per unit and sequence, workspace of the call, sized for the plan with the most units -- the plan is
+    // chosen by the slab, so the slab cannot wait for it
+    const int64_t part_bytes_per_seq = !h ? 0 : std::max<int64_t>(1, std::max(n_units(h, 8, W), n_units(h, 16, W))) * h->K * h->K * (int64_t)sizeof(double);
+    const auto prepare = [&](int units, int64_t nseq) { return h->pairs.ensure((size_t)std::max(units, 1) * (size_t)nseq * h->K * h->K * sizeof(double)); };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        phk::PArgs pa;
+        pa.lens = lens;
+        pa.part = (double*)h->pairs.p;
+        pa.counts = counts ? counts + (b0 * S + s0) * h->K * h->K : nullptr;
+        pa.row0 = 0;
+        return PHK_PICK(pairs, h)(T, nrm, a, pa, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, 1, Sweep("pair-count", validate, part_bytes_per_seq, prepare, launch));
 }
 
-// Viterbi decoding (phk_viterbi): the max-product forward kernel, then the traceback, per slab of the checkpoint store.  Like
-// posterior_impl it tunes and records nothing: the kernels have one layout per (real, K) and the handle's plan is not touched.
+// Viterbi decoding (phk_viterbi): the max-product forward kernel, then the traceback, per slab of the checkpoint store (same
+// bytes per sequence: delta every 8 sites in float64, every 16 in float32).  Like run_sweep it tunes and records nothing: the
+// kernels have one layout per (real, K) and the handle's plan is not touched.
 int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
                 int64_t B, int64_t S, int64_t W, const int64_t* lens, double* logp, uint8_t* path, int64_t path_stride, void* stream) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");
@@ -1859,81 +1823,40 @@ int phk_viterbi(phk_handle* h, const void* params, int64_t pstride_b, int64_t ps
     if (W < 0 || W >= h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld)", (long long)W, (long long)h->L);
     if (path_stride < h->L - W) return fail(PHK_EINVAL, "path_stride=%lld below L - W=%lld", (long long)path_stride, (long long)(h->L - W));
     if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
-    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
-    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    if (int rc = check_prefold(h, prefold, pstride_b, pstride_s); rc != PHK_OK) return rc;
     if (B == 0 || S == 0) return PHK_OK;
-    typedef hipError_t (*vit_fn)(int, const phk::KArgs&, const phk::VArgs&, int, hipStream_t);
-    vit_fn vit = nullptr;
-#define PHK_CASE(k) \
-    case k: vit = h->dbl ? phk::launch_viterbi_f64_##k : phk::launch_viterbi_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
+    const auto vit = PHK_PICK(viterbi, h);
     if (!vit) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
-    const size_t rs = real_size(h);
-    const int K = h->K;
+    const CallShape c = {params, pstride_b, pstride_s, prefold, inds, B, S, W, logp, stream};
 
-    // the checkpoint store is slabbed as for a gradient call (same bytes per sequence: delta every 8 sites in float64, every 16 in float32)
-    int64_t Bs = B, Ss = S;
-    {
-        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
-        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
-        if (B * S > max_seq) {
-            if (max_seq >= S) {
-                Bs = max_seq / S;
-            } else {
-                Bs = 1;
-                Ss = max_seq;
-            }
-        }
-        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
-    }
+    int64_t Bs, Ss;
+    if (int rc = slab_for(h, B, S, 0, &Bs, &Ss); rc != PHK_OK) return rc;
     HIP_TRY(hipMemsetAsync(path, 0xff, (size_t)(B * S * path_stride), st));  // what no sequence writes: past its own length
 
     for (int64_t b0 = 0; b0 < B; b0 += Bs) {
         const int64_t nb = std::min(Bs, B - b0);
         for (int64_t s0 = 0; s0 < S; s0 += Ss) {
             const int64_t ns = std::min(Ss, S - s0);
-            phk::KArgs a;
-            std::memset(&a, 0, sizeof(a));
-            a.packed = h->packed;
-            a.Lw = h->Lw;
-            a.Ltot = h->L;
-            a.W = W;
-            a.inds = inds + s0;
-            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
-            a.pstride_b = pstride_b;
-            a.pstride_s = pstride_s;
-            a.B = nb;
-            a.S = ns;
-            a.ll = logp + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
-            a.ckpt = h->ckpt.p;
-            a.risk = (int*)h->risk.p;
-            a.N = h->N;
-            a.pfstride_b = pstride_b / 7 * 5;
-            a.pfstride_s = pstride_s / 7 * 5;
-            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
-            {   // iteration budgets, twice what a healthy wave needs: one iteration per block (8 or 16 sites) in either kernel
-                const int64_t need = (h->L + 7) / 8 + 8;
-                for (int i = 0; i < 2; ++i)
-                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need * h->budget_num[i] / h->budget_den[i], INT32_MAX);
-            }
+            phk::KArgs a = base_kargs(h, c, b0, nb, s0, ns);
+            // iteration budgets: one iteration per block (8 or 16 sites) in either kernel
+            for (int i = 0; i < 2; ++i) a.loop_budget[i] = loop_budget(h, i, (h->L + 7) / 8 + 8);
             phk::VArgs d;
             d.lens = lens;
             d.path = path + (b0 * S + s0) * path_stride;
             d.path_stride = path_stride;
             hipError_t e = vit(h->nrm, a, d, 256, st);
-            if (e != hipSuccess) return fail(PHK_EHIP, "Viterbi kernel launch (K=%d): %s", K, hipGetErrorString(e));
+            if (e != hipSuccess) return fail(PHK_EHIP, "Viterbi kernel launch (K=%d): %s", h->K, hipGetErrorString(e));
         }
     }
     return PHK_OK;
 }
 
 // Posterior path sampling (phk_sample_paths): the forward leg of the plan a gradient call of this shape would run, launched as
-// posterior_impl launches it (same variant, same operators, no beta scan: ll is phk_posterior's to the bit), then the sampling
-// traceback.  Like posterior_impl it reads the plan and tunes and records nothing.
+// run_sweep launches it (same variant, same operators, no beta scan: ll is phk_posterior's to the bit), then the sampling
+// traceback.  Like run_sweep it reads the plan and tunes and records nothing.
 int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
                      int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, double* ll, uint8_t* paths, int64_t path_stride,
                      void* stream) {
@@ -1943,101 +1866,36 @@ int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64
     if (n_samples < 1 || n_samples > 65535) return fail(PHK_EINVAL, "n_samples=%lld outside [1, 65535]", (long long)n_samples);
     if (path_stride < h->L - W) return fail(PHK_EINVAL, "path_stride=%lld below L - W=%lld", (long long)path_stride, (long long)(h->L - W));
     if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
-    if (prefold && h->dbl) return fail(PHK_EINVAL, "pre-folded factors belong to the float32 kernels (the float64 kernels do not fold)");
-    if (prefold && (pstride_b % 7 != 0 || pstride_s % 7 != 0)) return fail(PHK_EINVAL, "parameter strides must be multiples of 7 (whole [7, K] blocks)");
+    if (int rc = check_prefold(h, prefold, pstride_b, pstride_s); rc != PHK_OK) return rc;
     if (B == 0 || S == 0) return PHK_OK;
     Launchers l;
     if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
-    typedef hipError_t (*smp_fn)(int, int, const phk::KArgs&, const phk::SArgs&, int, hipStream_t);
-    smp_fn smp = nullptr;
-#define PHK_CASE(k) \
-    case k: smp = h->dbl ? phk::launch_sample_f64_##k : phk::launch_sample_f32_##k; break;
-    switch (h->K) { PHK_CASE(4) PHK_CASE(8) PHK_CASE(16) PHK_CASE(32) PHK_CASE(64) }
-#undef PHK_CASE
-    if (!smp) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    const auto smp = PHK_PICK(sample, h);
     HIP_TRY(hipSetDevice(h->device));
     hipStream_t st = (hipStream_t)stream;
     h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
-    const size_t rs = real_size(h);
     const int K = h->K;
+    const CallShape c = {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream};
 
-    // the checkpoint store is slabbed as for a gradient call
-    int64_t Bs = B, Ss = S;
-    {
-        const int64_t per_seq = ((h->L + 7) / 8) * K * (int64_t)rs;
-        const int64_t max_seq = std::max<int64_t>(1, h->ws_limit / std::max<int64_t>(per_seq, 1));
-        if (B * S > max_seq) {
-            if (max_seq >= S) {
-                Bs = max_seq / S;
-            } else {
-                Bs = 1;
-                Ss = max_seq;
-            }
-        }
-        if (int rc = ensure_scratch(h, Bs * Ss); rc != PHK_OK) return rc;
-    }
-    const int64_t nseq_launch = std::min(Bs, B) * std::min(Ss, S);
-    Plan plan = adjust_hybrid(h, choose_plan(h, nseq_launch, W, 1), std::min(Bs, B));
-    const int Rf = plan.segmented ? plan.R1 : (plan.R1 ? plan.R1 : plan.R);  // the forward leg's variant
-    if (!valid_Rf(h, Rf) || !valid_T(K, Rf, plan.T)) return fail(PHK_EINVAL, "forward variant R=%d T=%d not available for K=%d", Rf, plan.T, K);
+    int64_t Bs, Ss;
+    if (int rc = slab_for(h, B, S, 0, &Bs, &Ss); rc != PHK_OK) return rc;
+    Plan plan;
+    int Rf;
+    if (int rc = read_plan(h, Bs, Ss, W, &plan, &Rf); rc != PHK_OK) return rc;
     const bool dense = dense_capable(h) && Rf == 16;
     if (dense) {
-        const int64_t blocks = std::min(Bs, B) * (pstride_s != 0 ? std::min(Ss, S) : 1);
-        if (int rc = h->ops.ensure((size_t)blocks * 2 * phk::DENSE_OPS_FLOATS * sizeof(float)); rc != PHK_OK) return rc;
+        if (int rc = size_dense_ops(h, c, Bs, Ss); rc != PHK_OK) return rc;
     }
 
     for (int64_t b0 = 0; b0 < B; b0 += Bs) {
         const int64_t nb = std::min(Bs, B - b0);
         for (int64_t s0 = 0; s0 < S; s0 += Ss) {
             const int64_t ns = std::min(Ss, S - s0);
-            phk::KArgs a;
-            a.packed = h->packed;
-            a.Lw = h->Lw;
-            a.Ltot = h->L;
-            a.W = W;
-            a.inds = inds + s0;
-            a.params = (const char*)params + (size_t)(b0 * pstride_b + s0 * pstride_s) * rs;
-            a.pstride_b = pstride_b;
-            a.pstride_s = pstride_s;
-            a.B = nb;
-            a.S = ns;
-            a.ll = ll + b0 * S + s0;  // (with Ss < S the slab is one particle: its rows are contiguous)
-            a.ckpt = h->ckpt.p;
-            a.aux = (phk::SeqAux*)h->aux.p;
-            a.grad = nullptr;
-            a.gacc = (double*)h->gacc.p;
-            a.grad_dlog = 0;
-            a.eblk = (int16_t*)h->eblk.p;
-            a.eseg = (int32_t*)h->eseg.p;
+            phk::KArgs a = base_kargs(h, c, b0, nb, s0, ns);
             a.seg_blocks = seg_blocks(plan.T);
-            a.bseg = h->bseg.p;
-            a.fseg = (const int32_t*)h->fseg.p;
-            a.bpi = (double*)h->bpi.p;
-            a.risk = (int*)h->risk.p;
-            a.seq_begin = a.seq_end = 0;
-            a.N = h->N;
-            a.part = nullptr;
-            a.ops_f = a.ops_b = nullptr;
-            a.asm_run = 0;
-            a.scan_prio = 0;
-            a.mask_runs = h->mask_runs;
-            a.pfstride_b = pstride_b / 7 * 5;
-            a.pfstride_s = pstride_s / 7 * 5;
-            a.prefold = prefold ? prefold + (b0 * a.pfstride_b + s0 * a.pfstride_s) : nullptr;
-            {   // iteration budgets, twice what a healthy wave needs (see enqueue); the traceback makes one iteration per block
-                const int64_t nblk = (h->L + plan.T - 1) / plan.T, npieces = h->Lw / 4;
-                const int64_t need[4] = {npieces + 2 * (64 / plan.T) + 8, nblk + 8, npieces + 16, nblk + 8};
-                const int scale_of[4] = {0, 1, 2, 1};
-                for (int i = 0; i < 4; ++i)
-                    a.loop_budget[i] = (int32_t)std::min<int64_t>(2 * need[i] * h->budget_num[scale_of[i]] / h->budget_den[scale_of[i]], INT32_MAX);
-            }
+            set_budgets(h, &a, plan.T, (h->L + plan.T - 1) / plan.T + 8);  // (the traceback makes one iteration per block)
             if (dense) {
-                if (pstride_s == 0 && s0 > 0) {
-                    a.ops_f = (const float*)h->ops.p;
-                    a.ops_b = a.ops_f + nb * phk::DENSE_OPS_FLOATS;
-                } else if (int rc = build_dense_ops(h, &a, st); rc != PHK_OK) {
-                    return rc;
-                }
+                if (int rc = slab_dense_ops(h, &a, s0, st); rc != PHK_OK) return rc;
             }
             phk::SArgs d;
             d.paths = paths;
@@ -2047,7 +1905,7 @@ int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64
             d.b0 = b0;
             d.s0 = s0;
             d.S_call = S;
-            // (the forward kernel of a segmented plan runs with the workgroup it has beside the beta scan, as in posterior_impl)
+            // (the forward kernel of a segmented plan runs with the workgroup it has beside the beta scan, as in run_sweep)
             hipError_t e = l.fwd(Rf, plan.T, h->nrm, true, a, plan.segmented ? 256 : FWD_NT, st);
             if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
             e = smp(plan.T, h->nrm, a, d, 256, st);

@@ -1,0 +1,84 @@
+// Arguments of the sweeps that run behind the forward pass, beside KArgs: one struct per sweep, shared between its kernels
+// (launch_<sweep>.hip) and the host side (phk_api.hip).  A layout is a kernel-argument layout: fields keep their order.
+#pragma once
+#include <stdint.h>
+
+namespace phk {
+
+// posterior decoding (launch_decode.hip)
+struct DArgs {
+    int64_t bin;           // scored sites per bin (>= 1)
+    int64_t nbin;          // bins per sequence: ceil((Ltot - W) / bin)
+    const double* values;  // [B|1, K] value of every state (row stride vstride_b; 0 = shared), or null (no mean)
+    int64_t vstride_b;
+    void* mean;            // [B, S, nbin] real: mean over the bin of sum_k values_k gamma_t(k), or null
+    void* marg;            // [B, S, nbin, K] real: mean over the bin of gamma_t, or null
+};
+
+// Viterbi decoding (launch_viterbi.hip)
+struct VArgs {
+    const int64_t* lens;  // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    uint8_t* path;        // [B, S, path_stride]: states at sites W .. len - 1, then 255
+    int64_t path_stride;  // >= Ltot - W
+};
+
+// path-sampling traceback (launch_sample.hip)
+struct SArgs {
+    uint8_t* paths;       // [B, S, n_samples, path_stride] of the CALL: states at sites W .. Ltot - 1
+    int64_t path_stride;  // >= Ltot - W
+    int64_t n_samples;    // samples per sequence (>= 1)
+    uint64_t seed;        // Philox key
+    int64_t b0, s0;       // position of the slab in the call, and ...
+    int64_t S_call;       // ... the call's S: q = (b0 + b) * S_call + (s0 + s) numbers the sequences of the call
+};
+
+// transition posteriors (launch_trans.hip)
+struct TArgs {
+    int64_t bin;          // scored sites per bin (>= 1)
+    int64_t nbin;         // bins per sequence: ceil((Ltot - W) / bin)
+    const int64_t* lens;  // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    void* arr;            // [B, S, nbin, 3, K] real: mean over the bin's own sites of (stay, up, down), or null
+    void* chg;            // [B, S, nbin, 2] real: sum over the bin's own sites of (sum_k up, sum_k down), or null
+};
+
+// leave-one-out predictive decoding (launch_loo.hip)
+struct LArgs {
+    int64_t bin;          // scored sites per bin (>= 1)
+    int64_t nbin;         // bins per sequence: ceil((Ltot - W) / bin)
+    const int64_t* lens;  // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    void* track;          // [B, S, nbin, 3] real: sums over the bin's own sites of (phet at observed sites, phet at missing
+                          // sites, log score)
+};
+
+// tract posteriors (launch_tract.hip)
+struct QArgs {
+    int64_t bin;            // scored sites per bin (>= 1)
+    int64_t nbin;           // bins per sequence: ceil((Ltot - W) / bin)
+    const int64_t* lens;    // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    const double* weights;  // [B, K] (row stride wstride_b) or [K] (wstride_b = 0): the per-state weight m in [0, 1]
+    int64_t wstride_b;
+    void* tract;            // [B, S, nbin] real: E[prod of m(z_t) over the bin's own sites | o]
+};
+
+// local likelihood-ratio scans (launch_local.hip)
+struct RArgs {
+    int64_t bin;           // scored sites per bin (>= 1)
+    int64_t nbin;          // bins per sequence: ceil((Ltot - W) / bin)
+    const int64_t* lens;   // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    const void* alt;       // [B, S|1, 7, K] real: the alternative blocks, laid out like KArgs::params (their pi row is not read)
+    int64_t astride_b;     // element strides of alt
+    int64_t astride_s;     // 0: one block per particle, broadcast over chunks
+    const float* alt_prefold;  // pre-folded factors of the alternative blocks [B, S|1, 5, K] (float32 kernels), or null
+    int64_t apfstride_b, apfstride_s;
+    void* logratio;        // [B, S, nbin] real: log P(o | bin under the alternative) - log P(o)
+};
+
+// pair counts (launch_pairs.hip)
+struct PArgs {
+    const int64_t* lens;  // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    double* part;         // workspace [max(units, 1), B S of the launch, K, K]: every unit's own sum of raw outer products
+    double* counts;       // [B, S, K, K] of the launch, the caller's order: expected moves from state i (first) to state j
+    int row0;             // first origin state of the row tile this launch accumulates (set by the launcher; 0 on the matrix path)
+};
+
+}  // namespace phk

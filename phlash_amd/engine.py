@@ -9,6 +9,7 @@ streams); all arithmetic on the path happens in the HIP kernels.
 from __future__ import annotations
 
 import ctypes
+from typing import NamedTuple
 
 import numpy as np
 import torch
@@ -17,6 +18,19 @@ from . import _lib
 
 
 COMPILED_K = (4, 8, 16, 32, 64)
+
+
+class _SweepCall(NamedTuple):
+    """The arguments the sweeps' C entry points share (``HipEngine._sweep_call``)."""
+
+    head: tuple  # handle, params, pstride_b, pstride_s, prefold
+    grid: tuple  # inds, B, S
+    B: int
+    S: int
+    pad_k: int  # padding states beyond the caller's K
+    lens: int | None  # device pointer
+    stream: ctypes.c_void_p
+    keep: tuple  # the tensors behind the pointers: alive until the call is enqueued
 
 
 class HipEngine:
@@ -191,16 +205,58 @@ class HipEngine:
         return f.value, b.value, n.value
 
     # ---- the operator -----------------------------------------------------------------------
+    def _pad_states(self, blocks: torch.Tensor) -> torch.Tensor:
+        """Parameter blocks [.., .., 7, K_user] padded to the compiled size: rows b, d, u, v, pi with 0, emission rows with 1."""
+        if self.K_user == self.K:
+            return blocks
+        pad = torch.zeros(blocks.shape[:3] + (self.K - self.K_user,), dtype=blocks.dtype, device=blocks.device)
+        pad[:, :, 4:6, :] = 1.0
+        return torch.cat([blocks, pad], -1)
+
+    def _blocks(self, x: torch.Tensor, stream: ctypes.c_void_p):
+        """Blocks [nb, ns, 7, K] -> (the blocks in the handle's float type, their pre-folded factors or None).  float64 blocks
+        for a float32 kernel object: one launch rounds them AND forms the folded factors the float32 kernels run on in
+        float64, rounded once (phk_prefold; the kernels would otherwise fold the rounded rows)."""
+        if x.dtype == torch.float64 and not self.double_precision and self.prefold:
+            x64 = x.contiguous()
+            p = torch.empty(x64.shape, dtype=torch.float32, device=self.device)
+            pf = torch.empty(x64.shape[:2] + (5, self.K), dtype=torch.float32, device=self.device)
+            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, x64.data_ptr(), x64.shape[0] * x64.shape[1], p.data_ptr(),
+                                               pf.data_ptr(), None, stream))
+            return p, pf
+        return x.to(self.dtype).contiguous(), None
+
+    def _sweep_call(self, params: torch.Tensor, inds: torch.Tensor, lens: torch.Tensor | None = None) -> "_SweepCall":
+        """What every sweep behind the forward pass does with ``params`` / ``inds`` / ``lens`` (as ``run`` takes them) before
+        its C call: checks, padding to the compiled K, the float type of the handle."""
+        assert params.is_cuda and inds.is_cuda and params.device == self.device
+        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
+        B, Sp = params.shape[0], params.shape[1]
+        S = inds.shape[0]
+        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        params = self._pad_states(params)
+        if lens is not None:
+            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
+            lens = lens.contiguous()
+        stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+        p, pf = self._blocks(params, stream)
+        inds = inds.contiguous()
+        return _SweepCall(
+            head=(self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None),
+            grid=(inds.data_ptr(), B, S), B=B, S=S, pad_k=self.K - self.K_user, lens=lens.data_ptr() if lens is not None else None,
+            stream=stream, keep=(p, pf, inds, lens),
+        )
+
+    def _nbin(self, warmup: int, bin: int) -> int:
+        return (self.L - int(warmup) + int(bin) - 1) // int(bin)
+
     def run(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, grad: bool = True, dlog: bool = False):
         """params [B, S, 7, K] or [B, 1, 7, K] (one block per particle, broadcast over the chunks);
         inds int64 [S] on the device.  Returns ll [B, S] float64 and, if ``grad``, d ll/d params
         [B, S, 7, K] in the handle's float type (``dlog``: theta * d ll/d theta)."""
         assert params.is_cuda and inds.is_cuda and params.device == self.device
         assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
-        if self.K_user != self.K:  # pad to the compiled size: rows b,d,u,v,pi with 0, emission rows with 1
-            pad = torch.zeros(params.shape[:3] + (self.K - self.K_user,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
+        params = self._pad_states(params)
         assert inds.ndim == 1 and inds.dtype == torch.int64
         B, Sp = params.shape[0], params.shape[1]
         S = inds.shape[0]
@@ -249,18 +305,10 @@ class HipEngine:
         type, over bins of ``bin`` scored sites (nbin = ceil((L - warmup) / bin)): the bin means of gamma_t and of
         sum_k values_k gamma_t(k).  ``values`` [K] or [B, K] (float64 on the device) is required for ``mean``.  Padded
         states (K below the compiled size) get value 0 and posterior 0; they are stripped from ``marginals``."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert marginals or mean, "nothing to decode: marginals and mean are both off"
         assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
+        c = self._sweep_call(params, inds)
+        B, S = c.B, c.S
         vals, vstride = None, 0
         if mean:
             assert values is not None, "mean needs values"
@@ -268,32 +316,20 @@ class HipEngine:
             assert vals.shape[-1] == self.K_user and vals.ndim in (1, 2), vals.shape
             if vals.ndim == 2:
                 assert vals.shape[0] == B
-            if pad_k:
-                vals = torch.cat([vals, vals.new_zeros(vals.shape[:-1] + (pad_k,))], -1)
+            if c.pad_k:
+                vals = torch.cat([vals, vals.new_zeros(vals.shape[:-1] + (c.pad_k,))], -1)
             vals = vals.contiguous()
             vstride = self.K if vals.ndim == 2 else 0
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
-        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        nbin = self._nbin(warmup, bin)
         ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
         m = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device) if mean else None
         g = torch.empty((B, S, nbin, self.K), dtype=self.dtype, device=self.device) if marginals else None
         rc = _lib.load().phk_posterior(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), int(bin), vals.data_ptr() if vals is not None else None, vstride,
-            ll.data_ptr(), m.data_ptr() if m is not None else None, g.data_ptr() if g is not None else None, ctypes.c_void_p(stream),
+            *c.head, *c.grid, int(warmup), int(bin), vals.data_ptr() if vals is not None else None, vstride,
+            ll.data_ptr(), m.data_ptr() if m is not None else None, g.data_ptr() if g is not None else None, c.stream,
         )
         _lib.check(rc)
-        if g is not None and pad_k:
+        if g is not None and c.pad_k:
             g = g[..., : self.K_user]
         return ll, m, g
 
@@ -305,87 +341,37 @@ class HipEngine:
         state and the bin means of (stay, up, down) per state.  ``lens`` (int64 [N] on the device, one own length per data
         row of the engine, ``warmup < len <= L``): sites at or past a row's own length count nothing.  Padded states (K below
         the compiled size) have no mass; they are stripped from ``arrivals``."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert arrivals or changes, "nothing to compute: arrivals and changes are both off"
         assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
-        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        c = self._sweep_call(params, inds, lens)
+        B, S = c.B, c.S
+        nbin = self._nbin(warmup, bin)
         ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        c = torch.empty((B, S, nbin, 2), dtype=self.dtype, device=self.device) if changes else None
+        chg = torch.empty((B, S, nbin, 2), dtype=self.dtype, device=self.device) if changes else None
         a = torch.empty((B, S, nbin, 3, self.K), dtype=self.dtype, device=self.device) if arrivals else None
         rc = _lib.load().phk_transitions(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), int(bin), lens.data_ptr() if lens is not None else None, ll.data_ptr(),
-            a.data_ptr() if a is not None else None, c.data_ptr() if c is not None else None, ctypes.c_void_p(stream),
+            *c.head, *c.grid, int(warmup), int(bin), c.lens, ll.data_ptr(),
+            a.data_ptr() if a is not None else None, chg.data_ptr() if chg is not None else None, c.stream,
         )
         _lib.check(rc)
-        if a is not None and pad_k:
+        if a is not None and c.pad_k:
             a = a[..., : self.K_user]
-        return ll, c, a
+        return ll, chg, a
 
     def pair_counts(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, lens: torch.Tensor | None = None):
         """Pair counts (``phk_pair_counts``): params / inds as ``run``.  Returns (ll [B, S] float64, counts [B, S, K, K] float64,
         origin state first): the pair posterior P(z_prev = i, z_t = j | o) summed over every row's own scored sites, the expected
         number of moves from state i to state j.  ``lens`` as ``transitions``.  Padded states (K below the compiled size) have no
         mass; they are stripped."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
-        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        c = torch.empty((B, S, self.K, self.K), dtype=torch.float64, device=self.device)
-        rc = _lib.load().phk_pair_counts(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), lens.data_ptr() if lens is not None else None, ll.data_ptr(), c.data_ptr(),
-            ctypes.c_void_p(stream),
-        )
+        c = self._sweep_call(params, inds, lens)
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        counts = torch.empty((c.B, c.S, self.K, self.K), dtype=torch.float64, device=self.device)
+        rc = _lib.load().phk_pair_counts(*c.head, *c.grid, int(warmup), c.lens, ll.data_ptr(), counts.data_ptr(), c.stream)
         _lib.check(rc)
-        if pad_k:
-            c = c[..., : self.K_user, : self.K_user]
-        return ll, c
+        if c.pad_k:
+            counts = counts[..., : self.K_user, : self.K_user]
+        return ll, counts
 
     def predictive(self, params: torch.Tensor, inds: torch.Tensor, warmup: int = 0, bin: int = 1, lens: torch.Tensor | None = None):
         """Leave-one-out predictive decoding (``phk_predictive``): params / inds as ``run``.  Returns (ll [B, S] float64, track
@@ -393,38 +379,13 @@ class HipEngine:
         bin sums of P(o_t = het | the row's other sites) over the observed sites, of the same over the missing sites, and of
         the log predictive of the observed sites at their own observations.  ``lens`` (int64 [N] on the device, one own length
         per data row of the engine, ``warmup < len <= L``): sites at or past a row's own length count nothing."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
-        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
-        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        track = torch.empty((B, S, nbin, 3), dtype=self.dtype, device=self.device)
+        c = self._sweep_call(params, inds, lens)
+        nbin = self._nbin(warmup, bin)
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        track = torch.empty((c.B, c.S, nbin, 3), dtype=self.dtype, device=self.device)
         rc = _lib.load().phk_predictive(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), int(bin), lens.data_ptr() if lens is not None else None, ll.data_ptr(),
-            track.data_ptr() if nbin > 0 else None, ctypes.c_void_p(stream),
+            *c.head, *c.grid, int(warmup), int(bin), c.lens, ll.data_ptr(), track.data_ptr() if nbin > 0 else None, c.stream,
         )
         _lib.check(rc)
         return ll, track
@@ -437,43 +398,19 @@ class HipEngine:
         E[prod of m(z_t) over the bin's sites | o], for an indicator the posterior probability that every site of the bin has
         its state in the set.  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
         L``): a site at or past a row's own length restricts nothing, a bin without a site of the row's own is 0."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
         assert weights.is_cuda and weights.device == self.device and weights.dtype == torch.float64, "weights: float64 on the device"
-        assert weights.shape in ((self.K_user,), (B, self.K_user)), f"weights: [K] or [B, K], got {tuple(weights.shape)}"
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-            weights = torch.cat([weights, torch.zeros(weights.shape[:-1] + (pad_k,), dtype=weights.dtype, device=weights.device)], -1)
+        assert weights.shape in ((self.K_user,), (params.shape[0], self.K_user)), f"weights: [K] or [B, K], got {tuple(weights.shape)}"
+        c = self._sweep_call(params, inds, lens)
+        if c.pad_k:
+            weights = torch.cat([weights, torch.zeros(weights.shape[:-1] + (c.pad_k,), dtype=weights.dtype, device=weights.device)], -1)
         weights = weights.contiguous()
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
-        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
-        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        tract = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device)
+        nbin = self._nbin(warmup, bin)
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        tract = torch.empty((c.B, c.S, nbin), dtype=self.dtype, device=self.device)
         rc = _lib.load().phk_tracts(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), int(bin), weights.data_ptr(), self.K if weights.ndim == 2 else 0,
-            lens.data_ptr() if lens is not None else None, ll.data_ptr(), tract.data_ptr() if nbin > 0 else None,
-            ctypes.c_void_p(stream),
+            *c.head, *c.grid, int(warmup), int(bin), weights.data_ptr(), self.K if weights.ndim == 2 else 0,
+            c.lens, ll.data_ptr(), tract.data_ptr() if nbin > 0 else None, c.stream,
         )
         _lib.check(rc)
         return ll, tract
@@ -486,51 +423,21 @@ class HipEngine:
         (nbin = ceil((L - warmup) / bin)): per bin log P(o | the bin's sites under the alternative, the rest under params) -
         log P(o | params).  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
         L``): a site at or past a row's own length is stepped with the fitted model, a bin without a site of the row's own is 0."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
+        c = self._sweep_call(params, inds, lens)
+        B, S = c.B, c.S
         assert alt.is_cuda and alt.device == self.device
         assert alt.ndim == 4 and alt.shape[2] == 7 and alt.shape[3] == self.K_user, alt.shape
         Ba, Sa = alt.shape[0], alt.shape[1]
         assert Ba in (1, B) and Sa in (1, S), f"alt: [{B}|1, {S}|1, 7, K], got {tuple(alt.shape)}"
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-            pad = torch.zeros(alt.shape[:3] + (pad_k,), dtype=alt.dtype, device=alt.device)
-            pad[:, :, 4:6, :] = 1.0
-            alt = torch.cat([alt, pad], -1)
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-
-        def blocks(x, nb, ns):  # -> (blocks in the handle's float type, pre-folded factors or None)
-            if x.dtype == torch.float64 and not self.double_precision and self.prefold:
-                x64 = x.contiguous()
-                p = torch.empty(x64.shape, dtype=torch.float32, device=self.device)
-                pf = torch.empty((nb, ns, 5, self.K), dtype=torch.float32, device=self.device)
-                _lib.check(_lib.load().phk_prefold(self.device.index, self.K, x64.data_ptr(), nb * ns, p.data_ptr(), pf.data_ptr(),
-                                                   None, ctypes.c_void_p(stream)))
-                return p, pf
-            return x.to(self.dtype).contiguous(), None
-
-        p, pf = blocks(params, B, Sp)
-        a, apf = blocks(alt, Ba, Sa)
-        inds = inds.contiguous()
-        nbin = (self.L - int(warmup) + int(bin) - 1) // int(bin)
+        a, apf = self._blocks(self._pad_states(alt), c.stream)
+        nbin = self._nbin(warmup, bin)
         ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
         out = torch.empty((B, S, nbin), dtype=self.dtype, device=self.device)
         rc = _lib.load().phk_local_ratio(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            a.data_ptr(), Sa * 7 * self.K if Ba == B and B > 1 else 0, 7 * self.K if Sa == S and S > 1 else 0,
-            apf.data_ptr() if apf is not None else None, inds.data_ptr(), B, S, int(warmup), int(bin),
-            lens.data_ptr() if lens is not None else None, ll.data_ptr(), out.data_ptr() if nbin > 0 else None,
-            ctypes.c_void_p(stream),
+            *c.head, a.data_ptr(), Sa * 7 * self.K if Ba == B and B > 1 else 0, 7 * self.K if Sa == S and S > 1 else 0,
+            apf.data_ptr() if apf is not None else None, *c.grid, int(warmup), int(bin),
+            c.lens, ll.data_ptr(), out.data_ptr() if nbin > 0 else None, c.stream,
         )
         _lib.check(rc)
         return ll, out
@@ -541,39 +448,12 @@ class HipEngine:
         ``warmup .. L - 1``.  ``lens`` (int64 [N] on the device, one own length per data row of the engine, ``warmup < len <=
         L``) cuts every row at its own length: bytes of ``path`` past it are 255.  Padded states (K below the compiled size)
         are unreachable and never appear in a path."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert 0 <= int(warmup) < self.L
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-        if lens is not None:
-            assert lens.is_cuda and lens.device == self.device and lens.dtype == torch.int64 and lens.shape == (self.N,), "lens: int64 [N] on the device"
-            lens = lens.contiguous()
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
+        c = self._sweep_call(params, inds, lens)
         n_out = self.L - int(warmup)
-        logp = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        path = torch.empty((B, S, n_out), dtype=torch.uint8, device=self.device)
-        rc = _lib.load().phk_viterbi(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), lens.data_ptr() if lens is not None else None, logp.data_ptr(), path.data_ptr(),
-            n_out, ctypes.c_void_p(stream),
-        )
+        logp = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        path = torch.empty((c.B, c.S, n_out), dtype=torch.uint8, device=self.device)
+        rc = _lib.load().phk_viterbi(*c.head, *c.grid, int(warmup), c.lens, logp.data_ptr(), path.data_ptr(), n_out, c.stream)
         _lib.check(rc)
         return logp, path
 
@@ -583,35 +463,13 @@ class HipEngine:
         (the warm-up sites condition the draws).  Draw r of sequence (b, s) of the call is a function of ``seed``, b * S + s, r
         and the site alone (a counter-based generator).  Padded states (K below the compiled size) have no mass and are never
         drawn."""
-        assert params.is_cuda and inds.is_cuda and params.device == self.device
-        assert params.ndim == 4 and params.shape[2] == 7 and params.shape[3] == self.K_user, params.shape
         assert 0 <= int(warmup) < self.L and 1 <= int(n_samples) <= 65535 and 0 <= int(seed) < 1 << 64
-        B, Sp = params.shape[0], params.shape[1]
-        S = inds.shape[0]
-        assert inds.ndim == 1 and inds.dtype == torch.int64 and Sp in (1, S)
-        pad_k = self.K - self.K_user
-        if pad_k:
-            pad = torch.zeros(params.shape[:3] + (pad_k,), dtype=params.dtype, device=params.device)
-            pad[:, :, 4:6, :] = 1.0
-            params = torch.cat([params, pad], -1)
-        stream = torch.cuda.current_stream(self.device).cuda_stream
-        pf = None
-        if params.dtype == torch.float64 and not self.double_precision and self.prefold:
-            p64 = params.contiguous()
-            p = torch.empty(p64.shape, dtype=torch.float32, device=self.device)
-            pf = torch.empty((B, Sp, 5, self.K), dtype=torch.float32, device=self.device)
-            _lib.check(_lib.load().phk_prefold(self.device.index, self.K, p64.data_ptr(), B * Sp, p.data_ptr(), pf.data_ptr(),
-                                               None, ctypes.c_void_p(stream)))
-        else:
-            p = params.to(self.dtype).contiguous()
-        inds = inds.contiguous()
+        c = self._sweep_call(params, inds)
         n_out = self.L - int(warmup)
-        ll = torch.empty((B, S), dtype=torch.float64, device=self.device)
-        paths = torch.empty((B, S, int(n_samples), n_out), dtype=torch.uint8, device=self.device)
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        paths = torch.empty((c.B, c.S, int(n_samples), n_out), dtype=torch.uint8, device=self.device)
         rc = _lib.load().phk_sample_paths(
-            self._h, p.data_ptr(), Sp * 7 * self.K, 7 * self.K if Sp == S else 0, pf.data_ptr() if pf is not None else None,
-            inds.data_ptr(), B, S, int(warmup), int(n_samples), int(seed), ll.data_ptr(), paths.data_ptr(), n_out,
-            ctypes.c_void_p(stream),
+            *c.head, *c.grid, int(warmup), int(n_samples), int(seed), ll.data_ptr(), paths.data_ptr(), n_out, c.stream,
         )
         _lib.check(rc)
         return ll, paths

@@ -35,101 +35,21 @@ def _as_tensor(a, device):
     return torch.as_tensor(np.asarray(a, dtype=np.float64), dtype=F64, device=device)
 
 
-def _run_guarded(kern, *args, **kw):
-    """engine.run with the safety net of the rescale interval: if the forward kernel reports that the
-    parameters are too extreme for rescaling every few sites only, switch this kernel object to
+def _guarded(kern, method: str, *args, **kw):
+    """engine.<method> (``run`` or a sweep) with the safety net of the rescale interval: if the forward kernel reports that
+    the parameters are too extreme for rescaling every few sites only, switch this kernel object to
     per-site rescaling (the reference's schedule, hmm.py:77-79) for good and evaluate again.
     Rank-local on purpose: ``loglik`` / ``__call__`` contain no collective, so a rank may redo its own
     evaluation without its peers.  The sharded evaluation (``parallel.py``, used by ``fit``) must NOT
     decide locally -- its redo contains an all-reduce -- and carries the flags in that all-reduce
     instead (``take_flags_into`` / ``check_rescaling(collective=True)``).  A chunk index outside
-    [0, N) surfaces here as AssertionError (gpu.py:197-199)."""
-    out = kern._eng.run(*args, **kw)
+    [0, N) surfaces here as AssertionError (gpu.py:197-199).  Every sweep raises the same underflow flag (path sampling
+    also for a draw whose weights have no mass)."""
+    out = getattr(kern._eng, method)(*args, **kw)
     if kern._eng.underflow_risk():
         warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
         kern._eng.set_rescale_interval(1)
-        out = kern._eng.run(*args, **kw)
-    return out
-
-
-def _posterior_guarded(kern, *args, **kw):
-    """engine.posterior with the same safety net as ``_run_guarded`` (the decode sweep raises the same underflow flag)."""
-    out = kern._eng.posterior(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.posterior(*args, **kw)
-    return out
-
-
-def _transitions_guarded(kern, *args, **kw):
-    """engine.transitions with the same safety net as ``_run_guarded`` (the transition sweep raises the same underflow flag)."""
-    out = kern._eng.transitions(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.transitions(*args, **kw)
-    return out
-
-
-def _pair_counts_guarded(kern, *args, **kw):
-    """engine.pair_counts with the same safety net as ``_run_guarded`` (the pair-count sweep raises the same underflow flag)."""
-    out = kern._eng.pair_counts(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.pair_counts(*args, **kw)
-    return out
-
-
-def _predictive_guarded(kern, *args, **kw):
-    """engine.predictive with the same safety net as ``_run_guarded`` (the predictive sweep raises the same underflow flag)."""
-    out = kern._eng.predictive(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.predictive(*args, **kw)
-    return out
-
-
-def _tracts_guarded(kern, *args, **kw):
-    """engine.tracts with the same safety net as ``_run_guarded`` (the tract sweep raises the same underflow flag)."""
-    out = kern._eng.tracts(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.tracts(*args, **kw)
-    return out
-
-
-def _local_guarded(kern, *args, **kw):
-    """engine.local_ratio with the same safety net as ``_run_guarded`` (the local-ratio sweep raises the same underflow flag)."""
-    out = kern._eng.local_ratio(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.local_ratio(*args, **kw)
-    return out
-
-
-def _viterbi_guarded(kern, *args, **kw):
-    """engine.viterbi with the same safety net as ``_run_guarded`` (the max-product recursion raises the same underflow flag)."""
-    out = kern._eng.viterbi(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.viterbi(*args, **kw)
-    return out
-
-
-def _sample_guarded(kern, *args, **kw):
-    """engine.sample_paths with the same safety net as ``_run_guarded`` (the forward kernel raises the same underflow flag, and so
-    does a draw whose weights have no mass)."""
-    out = kern._eng.sample_paths(*args, **kw)
-    if kern._eng.underflow_risk():
-        warnings.warn("extreme HMM parameters: switching to per-site rescaling for this kernel object")
-        kern._eng.set_rescale_interval(1)
-        out = kern._eng.sample_paths(*args, **kw)
+        out = getattr(kern._eng, method)(*args, **kw)
     return out
 
 
@@ -202,11 +122,11 @@ class _LogLik(torch.autograd.Function):
     def forward(ctx, params, kern, inds, need_grad):
         # params [B, S|1, 7, K] float64 on the device
         if need_grad:
-            ll, g = _run_guarded(kern, params, inds, warmup=kern.overlap, grad=True, dlog=False)
+            ll, g = _guarded(kern, "run", params, inds, warmup=kern.overlap, grad=True, dlog=False)
             ctx.save_for_backward(g)
             ctx.bcast = params.shape[1] == 1 and inds.shape[0] > 1
         else:
-            ll = _run_guarded(kern, params, inds, warmup=kern.overlap, grad=False)
+            ll = _guarded(kern, "run", params, inds, warmup=kern.overlap, grad=False)
         return ll
 
     @staticmethod
@@ -303,6 +223,22 @@ class PSMCKernel:
         assert bool(torch.isfinite(pa).all()), "not all parameters finite"  # gpu.py:214
         return pa, inds, added_B, added_S
 
+    def _model_inputs(self, pp, index):
+        """``_prepare`` for a model given as PSMCParams or DemographicModel (convenience overload, gpu.py:364-367)."""
+        if isinstance(pp, DemographicModel):
+            pp = PSMCParams.from_dm(pp)
+        return self._prepare(PSMCParams(*(_as_tensor(a, self.device) for a in pp)), index)
+
+    def _lens_tensor(self, lens):
+        """``lens`` ([N] integers, one own length per data row, ``overlap < len <= L``) as int64 on the device, or None."""
+        if lens is None:
+            return None
+        lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
+                               dtype=torch.int64, device=self.device)
+        assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
+        assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
+        return lens
+
     @staticmethod
     def _strip(x, added_B, added_S):
         # gpu.py:318-325
@@ -319,11 +255,7 @@ class PSMCKernel:
         """Log-likelihood of chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel;
         fields [M], [S, M], [B, S, M], or [B, 1, M] = one block per particle broadcast over the chunks).  Returns a float64 tensor
         of shape (), [S] or [B, S], differentiable w.r.t. the fields of ``pp`` by autograd."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)  # convenience overload, gpu.py:364-367
-        dev = self.device
-        fields = [_as_tensor(a, dev) for a in pp]
-        pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+        pa, inds, added_B, added_S = self._model_inputs(pp, index)
         need_grad = torch.is_grad_enabled() and pa.requires_grad
         ll = _LogLik.apply(pa, self, inds, need_grad)
         return self._strip(ll, added_B, added_S)
@@ -338,9 +270,9 @@ class PSMCKernel:
         pa, inds, added_B, added_S = self._prepare(pp, index)
         with torch.no_grad():
             if grad:
-                ll, g = _run_guarded(self, pa, inds, warmup=self.overlap, grad=True, dlog=True)
+                ll, g = _guarded(self, "run", pa, inds, warmup=self.overlap, grad=True, dlog=True)
             else:
-                ll = _run_guarded(self, pa, inds, warmup=self.overlap, grad=False)
+                ll = _guarded(self, "run", pa, inds, warmup=self.overlap, grad=False)
         ll = self._strip(ll, added_B, added_S)
         if want_numpy:
             ll = ll.cpu().numpy()
@@ -359,17 +291,14 @@ class PSMCKernel:
         [B, M]: a value per state, e.g. ``dm.eta.ect()``), ``mean`` [..., nbin] = bin means of sum_k values_k gamma_t(k).
         nbin = ceil((L - overlap) / bin).  Returns ``Posterior(ll, mean, marginals)``, device tensors in ``float_type``
         (ll float64); no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
             vals = None
             if values is not None:
                 vals = _as_tensor(values, self.device)
                 if vals.ndim == 2 and vals.shape[0] == 1:
                     vals = vals[0]
-            ll, m, g = _posterior_guarded(self, pa, inds, warmup=self.overlap, values=vals, bin=int(bin),
+            ll, m, g = _guarded(self, "posterior", pa, inds, warmup=self.overlap, values=vals, bin=int(bin),
                                           marginals=bool(marginals), mean=vals is not None)
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Posterior(strip(ll), strip(m), strip(g))
@@ -386,17 +315,10 @@ class PSMCKernel:
         per row of the kernel's data, ``overlap < len <= L``): sites at or past a row's own length add nothing and are not
         counted in a mean.  Returns ``Transitions(ll, changes, arrivals)``, device tensors in ``float_type`` (ll float64);
         no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            ll, c, a = _transitions_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens, arrivals=bool(arrivals))
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            lens = self._lens_tensor(lens)
+            ll, c, a = _guarded(self, "transitions", pa, inds, warmup=self.overlap, bin=int(bin), lens=lens, arrivals=bool(arrivals))
         strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
         return Transitions(strip(ll), strip(c), strip(a))
 
@@ -410,17 +332,10 @@ class PSMCKernel:
         ``loglik``).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <= L``): sites at or
         past a row's own length add nothing.  Returns ``PairCounts(ll, counts)``, float64 device tensors for either
         ``float_type``; no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            ll, c = _pair_counts_guarded(self, pa, inds, warmup=self.overlap, lens=lens)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            lens = self._lens_tensor(lens)
+            ll, c = _guarded(self, "pair_counts", pa, inds, warmup=self.overlap, lens=lens)
         return PairCounts(self._strip(ll, added_B, added_S), self._strip(c, added_B, added_S))
 
     # ---- leave-one-out predictive -------------------------------------------------------------
@@ -434,17 +349,10 @@ class PSMCKernel:
         ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <=
         L``): sites at or past a row's own length add nothing.  Returns ``Predictive(ll, het_observed, het_missing, score)``,
         device tensors in ``float_type`` (ll float64); no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            ll, track = _predictive_guarded(self, pa, inds, warmup=self.overlap, bin=int(bin), lens=lens)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            lens = self._lens_tensor(lens)
+            ll, track = _guarded(self, "predictive", pa, inds, warmup=self.overlap, bin=int(bin), lens=lens)
         track = self._strip(track, added_B, added_S)
         return Predictive(self._strip(ll, added_B, added_S), track[..., 0], track[..., 1], track[..., 2])
 
@@ -458,21 +366,14 @@ class PSMCKernel:
         ``loglik``); nbin = ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data,
         ``overlap < len <= L``): a site at or past a row's own length restricts nothing, and a bin without a site of the row's
         own is 0.  Returns ``Tracts(ll, prob)``, device tensors in ``float_type`` (ll float64); no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
             w = torch.as_tensor(np.array(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64),
                                 dtype=torch.float64, device=self.device)
             assert w.shape in ((self.M,), (pa.shape[0], self.M)), f"weights: [{self.M}] or [{pa.shape[0]}, {self.M}], got {tuple(w.shape)}"
             assert bool(((w >= 0) & (w <= 1)).all()), "weights must lie in [0, 1]"
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            ll, tract = _tracts_guarded(self, pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
+            lens = self._lens_tensor(lens)
+            ll, tract = _guarded(self, "tracts", pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
         return Tracts(self._strip(ll, added_B, added_S), self._strip(tract, added_B, added_S))
 
     # ---- local likelihood-ratio scans ------------------------------------------------------------
@@ -491,13 +392,10 @@ class PSMCKernel:
         ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <=
         L``): a site at or past a row's own length is stepped with ``pp``, and a bin without a site of the row's own is 0.
         Returns ``LocalRatio(ll, log_ratio)``, device tensors in ``float_type`` (ll float64); no gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         if isinstance(alt, DemographicModel):
             alt = PSMCParams.from_dm(alt)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
             B, S, M = pa.shape[0], inds.shape[0], self.M
             al = torch.stack([_as_tensor(a, self.device) for a in alt], -2)
             assert al.shape[-2:] == (7, M) and 2 <= al.ndim <= 4, f"alt: fields [..., {M}], got {tuple(al.shape)}"
@@ -507,12 +405,8 @@ class PSMCKernel:
             elif al.ndim == 3:  # one block per chunk, as pp
                 al = al[None]
             assert al.shape[0] in (1, B) and al.shape[1] in (1, S), f"alt: batch shape of pp or broadcast to it, got {tuple(al.shape)}"
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            ll, lr = _local_guarded(self, pa, al, inds, warmup=self.overlap, bin=int(bin), lens=lens)
+            lens = self._lens_tensor(lens)
+            ll, lr = _guarded(self, "local_ratio", pa, al, inds, warmup=self.overlap, bin=int(bin), lens=lens)
         return LocalRatio(self._strip(ll, added_B, added_S), self._strip(lr, added_B, added_S))
 
     # ---- Viterbi decoding ---------------------------------------------------------------------
@@ -523,17 +417,10 @@ class PSMCKernel:
         ``logp`` the log probability of the whole path.  ``lens`` ([N] integers, one own length per row of the kernel's data,
         ``overlap < len <= L``): rows end at their own length -- which is not the same as padding them with missing windows
         -- and ``path`` holds 255 past it.  Ties go to the lowest state index.  No gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
-            if lens is not None:
-                lens = torch.as_tensor(np.asarray(lens.cpu() if isinstance(lens, torch.Tensor) else lens, dtype=np.int64),
-                                       dtype=torch.int64, device=self.device)
-                assert lens.shape == (self.N,), f"lens: one length per data row, [{self.N}]"
-                assert int(lens.min()) > self.overlap and int(lens.max()) <= self.L, f"overlap={self.overlap} < lens <= L={self.L}"
-            logp, path = _viterbi_guarded(self, pa, inds, warmup=self.overlap, lens=lens)
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            lens = self._lens_tensor(lens)
+            logp, path = _guarded(self, "viterbi", pa, inds, warmup=self.overlap, lens=lens)
         return Viterbi(self._strip(logp, added_B, added_S), self._strip(path, added_B, added_S))
 
     # ---- posterior path sampling ---------------------------------------------------------------
@@ -543,12 +430,9 @@ class PSMCKernel:
         uint8, the states at the scored sites (the ``overlap`` warm-up sites condition the draws and are not reported).
         Forward filtering, backward sampling; the uniforms come from a counter-based generator keyed by ``seed``: draw r of a
         sequence depends on (seed, the sequence's position in the call, r, site) only, not on ``n_samples``.  No gradient."""
-        if isinstance(pp, DemographicModel):
-            pp = PSMCParams.from_dm(pp)
         with torch.no_grad():
-            fields = [_as_tensor(a, self.device) for a in pp]
-            pa, inds, added_B, added_S = self._prepare(PSMCParams(*fields), index)
-            ll, paths = _sample_guarded(self, pa, inds, warmup=self.overlap, n_samples=int(n_samples), seed=int(seed))
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            ll, paths = _guarded(self, "sample_paths", pa, inds, warmup=self.overlap, n_samples=int(n_samples), seed=int(seed))
         return PathSample(self._strip(ll, added_B, added_S), self._strip(paths, added_B, added_S))
 
     # ---- fused evaluation used by the sampler -------------------------------------------------

@@ -2,6 +2,8 @@
 tests/test_model.py, tests/test_mcmc.py) re-expressed against ``phlash_amd`` with the CPU oracle
 in the role the pure-JAX path plays there."""
 
+import ctypes
+
 import numpy as np
 import pytest
 
@@ -369,3 +371,36 @@ def test_fused_step_matches_the_autograd_definition(rng, dbl, with_afs):
     assert kern._flags.tolist() == [0.0, 1.0]
     with pytest.raises(AssertionError):
         kern.check_rescaling(collective=True)
+
+
+_W_AT = {"phk_loglik": 7, "phk_local_ratio": 12}  # position of W (elsewhere 8); bin follows it where there is one
+_HAS_BIN = ("phk_posterior", "phk_transitions", "phk_predictive", "phk_tracts", "phk_local_ratio")
+
+
+@pytest.mark.parametrize("name", ["phk_loglik", "phk_loglik_prefolded", "phk_posterior", "phk_transitions", "phk_predictive",
+                                  "phk_tracts", "phk_local_ratio", "phk_pair_counts", "phk_viterbi", "phk_sample_paths"])
+def test_entry_points_refuse_bad_calls_with_their_own_words(data, name):
+    """Every entry point over the (particle, chunk) grid: a NULL handle, bin = 0 and W > L come back as PHK_EINVAL with the
+    text the C ABI has always given, before anything is enqueued (the pointers are never read)."""
+    from phlash_amd import _lib
+    from phlash_amd.engine import HipEngine
+
+    lib = _lib.load()
+    eng = HipEngine(16, data)
+    dummy = torch.zeros(8, dtype=torch.float64, device="cuda")
+    types = _lib.SIGNATURES[name][1]
+    good = [dummy.data_ptr() if t is ctypes.c_void_p else 7 for t in types]  # (7: whole [7, K] blocks as strides)
+    good[0] = eng._h
+    w_at = _W_AT.get(name, 8)
+
+    def call(**change):
+        a = list(good)
+        for k, v in change.items():
+            a[{"h": 0, "W": w_at, "bin": w_at + 1}[k]] = v
+        return getattr(lib, name)(*a), lib.phk_last_error().decode()
+
+    assert call(h=None) == (_lib.PHK_EINVAL, "handle is NULL")
+    closed = ")" if name in ("phk_viterbi", "phk_sample_paths") else "]"  # (their W = L has no site to report)
+    assert call(W=eng.L + 1) == (_lib.PHK_EINVAL, f"W={eng.L + 1} outside [0, L={eng.L}{closed}")
+    if name in _HAS_BIN:
+        assert call(bin=0) == (_lib.PHK_EINVAL, "bin=0 must be >= 1")

@@ -368,3 +368,52 @@ def test_install_plan_reproduces_another_handles_plan(monkeypatch):
     e = HipEngine(K, data)
     with pytest.raises(AssertionError):  # PHK_EINVAL: no forced serial plan to extend
         e.install_plan({"segmented": 0, "R": 2, "T": 8, "R_forward": 1, "R_scan": 0, "hybrid_first": 64, "R_segment_sweep": 3})
+
+
+_SWEEP_CALLS = {  # the eight sweeps behind the forward pass, as PSMCKernel exposes them
+    "posterior": lambda k, pp, inds, lens: k.posterior(pp, inds, values=np.arange(16.0), bin=7),
+    "viterbi": lambda k, pp, inds, lens: k.viterbi(pp, inds, lens=lens),
+    "sample_paths": lambda k, pp, inds, lens: k.sample_paths(pp, inds, n_samples=2, seed=11),
+    "transitions": lambda k, pp, inds, lens: k.transitions(pp, inds, bin=7, lens=lens),
+    "predictive": lambda k, pp, inds, lens: k.predictive(pp, inds, bin=7, lens=lens),
+    "tracts": lambda k, pp, inds, lens: k.tracts(pp, inds, weights=(np.arange(16) < 6).astype(float), bin=7, lens=lens),
+    "local_ratio": lambda k, pp, alt, inds, lens: k.local_ratio(pp, alt, inds, bin=7, lens=lens),
+    "pair_counts": lambda k, pp, inds, lens: k.pair_counts(pp, inds, lens=lens),
+}
+
+
+@pytest.mark.parametrize("method", list(_SWEEP_CALLS))
+def test_every_sweep_gives_the_same_bits_in_slabs(method):
+    """The sweeps share one slab / argument / launch path on the host (run_sweep and its helpers in phk_api.hip): every one of
+    them returns the same bits whether the checkpoint store holds the whole call or not, and none touches the plan.  float32,
+    K = 16, 4 rows of 700 sites, 3 particles broadcast over the 4 chunks, serial plan.  Limits: 128 KB, and what three
+    sequences' checkpoints take at this row length (88 blocks x 16 states x 4 bytes each: slabs of chunks, at most three
+    sequences per launch sequence -- at 700 sites 128 KB alone would hold all twelve)."""
+    from phlash_amd.kernel import get_kernel
+    from phlash_amd.params import PSMCParams
+    from phlash_amd.synth import particle_population
+
+    K, N, L, W, B = 16, 4, 700, 50, 3
+    rng = np.random.default_rng(21)
+    rows = (rng.random((N, L)) < 0.04).astype(np.int8)
+    rows.flat[rng.integers(0, rows.size, rows.size // 100)] = -1
+    rows[:, 0] = 1
+    kern = get_kernel(K, rows, double_precision=False, overlap=W)
+    eng = kern._eng
+    tmpl, x = particle_population(K, B + 1, seed=22, sigma=0.25)
+    models = PSMCParams.from_dm(tmpl.from_flat(x).to_dm())  # fields [B + 1, K]
+    pp = PSMCParams(*(a[:B, None] for a in models))  # [B, 1, K]: one block per particle, broadcast over the chunks
+    args = (pp,) + ((PSMCParams(*(a[B] for a in models)),) if method == "local_ratio" else ())  # (the alternative: one block)
+    inds, lens = np.arange(N), np.array([700, 613, 700, 97])
+    eng.set_plan(0, 4, 8, 4, 0)
+    kern(pp, inds, grad=True)
+    plan0 = eng.get_plan()
+    whole = _SWEEP_CALLS[method](kern, *args, inds, lens)
+    for limit in (1 << 17, 3 * ((L + 7) // 8) * K * 4):
+        eng.set_workspace_limit(limit)
+        cut = _SWEEP_CALLS[method](kern, *args, inds, lens)
+        eng.set_workspace_limit(1 << 40)
+        assert len(cut) == len(whole)
+        for name, a, b in zip(whole._fields, whole, cut):
+            assert torch.equal(a, b), (method, limit, name)
+    assert eng.get_plan() == plan0
