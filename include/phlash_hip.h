@@ -542,6 +542,16 @@ int phk_block_rescale_counts(phk_handle* h, int64_t* counts, int64_t n, int64_t*
 int phk_set_asm_run(phk_handle* h, int on);
 /* 1 if the handle's sweeps use that sequence, else 0. */
 int phk_get_asm_run(const phk_handle* h);
+/* The K = 16 float32 forward kernel with one lane per sequence, writing checkpoints (the forward phase of the headline shape), runs
+ * its lean 64-site pieces -- in waves that hold at most two observation rows and whose sequences fold -- through a hand-written
+ * instruction sequence (csrc/fwd_run_k16r1.inc, generated by scripts/gen_fwd_asm.py: Lane::fwd_site<false> operation for operation,
+ * an all-hom block without its per-site tests, no pairing moves, the checkpoint stores from a wave-uniform base).  It returns the same
+ * bits as the C++ body (tests/test_fwd_run.py).  on = 0, or PHK_FWD_RUN=0 in the environment when the handle is created, selects
+ * the C++ body.  Handles of other kernels have no such sequence: the flag stays 0 whatever is asked.  A library built with
+ * -DPHK_FWD_RUN=0 answers on = 1 with PHK_EUNSUPPORTED.  Default and timings: profiles/ab_fwd_run.txt. */
+int phk_set_fwd_run(phk_handle* h, int on);
+/* 1 if the handle's forward kernel uses that sequence, else 0. */
+int phk_get_fwd_run(const phk_handle* h);
 /* The same flag word handed over WITHOUT a host synchronisation: a one-thread kernel on `stream`
  * writes dst[0] = 1.0 if the underflow-risk bit is set (else 0.0), dst[1] = 1.0 if a chunk index was
  * outside [0, N) (else 0.0) -- `dst` is a device array of two doubles -- and clears the word.  The

@@ -58,6 +58,8 @@ SIGNATURES = {
     "phk_block_rescale_counts": (_i, [_vp, ctypes.POINTER(ctypes.c_int64), _i64, ctypes.POINTER(ctypes.c_int64)]),
     "phk_set_asm_run": (_i, [_vp, _i]),
     "phk_get_asm_run": (_i, [_vp]),
+    "phk_set_fwd_run": (_i, [_vp, _i]),
+    "phk_get_fwd_run": (_i, [_vp]),
     "phk_set_autotune": (_i, [_vp, _i]),
     "phk_set_backward_mode": (_i, [_vp, _i]),
     "phk_set_plan": (_i, [_vp, _i, _i, _i, _i, _i]),

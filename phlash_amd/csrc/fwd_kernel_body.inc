@@ -440,16 +440,63 @@
          // loop below: no wait for the checkpoint stores; each piece is landed before the next is requested)
          if (uni2 && lean_ok && lean_piece(blk)) {
              const ScalarPieces spA = scalar_pieces(pieces), spB = scalar_pieces_of_lane(pieces, 63);
-             PieceWords nA = spA[pc], nB = spB[pc];
-             do {
-                 PieceWords cA = nA, cB = nB;
-                 asm volatile("" : "+s"(cA.x), "+s"(cA.y), "+s"(cA.z), "+s"(cA.w), "+s"(cB.x), "+s"(cB.y), "+s"(cB.z), "+s"(cB.w) : : "memory");
-                 nA = spA[pc + 1 < npieces ? pc + 1 : npieces - 1];
-                 nB = spB[pc + 1 < npieces ? pc + 1 : npieces - 1];
-                 fold_piece((uint64_t)cA.x | ((uint64_t)cA.y << 32), (uint64_t)cA.z | ((uint64_t)cA.w << 32),
-                            (uint64_t)cB.x | ((uint64_t)cB.y << 32), (uint64_t)cB.z | ((uint64_t)cB.w << 32));
-                 ++pc;
-             } while (lean_piece(blk) && --budget >= 0);
+             [[maybe_unused]] bool ran = false;
+#if PHK_FWD_RUN
+             // K = 16, one lane per sequence, float32, with checkpoints: the whole run of lean pieces as ONE hand-written instruction
+             // sequence (scripts/gen_fwd_asm.py): the do-while below with fold_piece / fold_block inside it, operation for operation --
+             // an all-hom block without its eight per-site tests, a mixed block with them, under one register plan; the state's zero
+             // pairing and the store addresses are the generator's.  Same bits (tests/test_fwd_run.py).
+             if constexpr (sizeof(real) == 4 && K == 16 && R == 1 && T == 8 && NRM == 4 && CKPT && !PHK_KERNEL_MR) {
+                 static_assert(ONDEMAND && !FREG && BPC == 8 && NP == 8 && L::EROW == 16 && RISK_EXP == -64 && PHK_CK_NT == 1 && !PHK_EXP_NO_CKPT_STORE &&
+                                   !PHK_EXP_NO_BLOCK_RESCALE,
+                               "fwd_run_k16r1.inc: the sequence is the body of this configuration");
+                 if (A.fwd_run != 0) {
+                     auto uni32 = [](uint32_t x) { return (uint32_t)__builtin_amdgcn_readfirstlane((int)x); };
+                     const uint64_t pA = (uint64_t)spA, pB = (uint64_t)spB;
+                     const uint64_t cku = (uint64_t)((real*)A.ckpt + (int64_t)blk * ck_step), ebu = (uint64_t)(A.eblk + (int64_t)blk * nseq);
+                     const uint64_t ckstep_b = (uint64_t)(ck_step * (int64_t)sizeof(real)), ebstep_b = (uint64_t)(nseq * (int64_t)sizeof(int16_t));
+                     const uint32_t fr_pa_lo = uni32((uint32_t)pA), fr_pa_hi = uni32((uint32_t)(pA >> 32));
+                     const uint32_t fr_pb_lo = uni32((uint32_t)pB), fr_pb_hi = uni32((uint32_t)(pB >> 32));
+                     const uint32_t fr_cku_lo = uni32((uint32_t)cku), fr_cku_hi = uni32((uint32_t)(cku >> 32));
+                     const uint32_t fr_ebu_lo = uni32((uint32_t)ebu), fr_ebu_hi = uni32((uint32_t)(ebu >> 32));
+                     const uint32_t fr_ckstep_lo = uni32((uint32_t)ckstep_b), fr_ckstep_hi = uni32((uint32_t)(ckstep_b >> 32));
+                     const uint32_t fr_ebstep_lo = uni32((uint32_t)ebstep_b), fr_ebstep_hi = uni32((uint32_t)(ebstep_b >> 32));
+                     const uint64_t espstep_b = (uint64_t)(nseq * (int64_t)sizeof(int32_t));
+                     const uint64_t fr_espstep = ((uint64_t)uni32((uint32_t)(espstep_b >> 32)) << 32) | uni32((uint32_t)espstep_b);
+                     const uint64_t fr_act = __ballot(active), fr_rowb = __ballot(rowB);
+                     const uint32_t fr_off[4] = {ck_off, ck_off + ck_piece, ck_off + 2u * ck_piece, ck_off + 3u * ck_piece};  // (bytes; < 2^31: lean_ok)
+                     const uint32_t fr_sqoff = sq_off, fr_lds = (uint32_t)(uintptr_t)lane.etab;
+                     const int fr_npm1 = __builtin_amdgcn_readfirstlane(npieces - 1), fr_nfull = __builtin_amdgcn_readfirstlane(nfull);
+                     const int fr_blkw = __builtin_amdgcn_readfirstlane(blkW), fr_segb = __builtin_amdgcn_readfirstlane(A.seg_blocks);
+                     const uint32_t fr_thr = uni32(__builtin_bit_cast(uint32_t, real(1) / real(int64_t(1) << PHK_RESCALE_TRIGGER_EXP)));
+                     int fr_blk = __builtin_amdgcn_readfirstlane(blk), fr_pc = __builtin_amdgcn_readfirstlane(pc);
+                     int fr_budget = __builtin_amdgcn_readfirstlane(budget), fr_segl = __builtin_amdgcn_readfirstlane(seg_left);
+                     uint64_t fr_esp = (uint64_t)esp;
+                     const int blk0 = fr_blk;
+#include "fwd_run_k16r1.inc"
+                     blk = fr_blk;
+                     pc = fr_pc;
+                     budget = fr_budget;
+                     seg_left = fr_segl;
+                     esp = (int32_t*)fr_esp;
+                     ckp += (int64_t)(blk - blk0) * ck_step;
+                     ebp += (int64_t)(blk - blk0) * nseq;
+                     ran = true;
+                 }
+             }
+#endif
+             if (!ran) {
+                 PieceWords nA = spA[pc], nB = spB[pc];
+                 do {
+                     PieceWords cA = nA, cB = nB;
+                     asm volatile("" : "+s"(cA.x), "+s"(cA.y), "+s"(cA.z), "+s"(cA.w), "+s"(cB.x), "+s"(cB.y), "+s"(cB.z), "+s"(cB.w) : : "memory");
+                     nA = spA[pc + 1 < npieces ? pc + 1 : npieces - 1];
+                     nB = spB[pc + 1 < npieces ? pc + 1 : npieces - 1];
+                     fold_piece((uint64_t)cA.x | ((uint64_t)cA.y << 32), (uint64_t)cA.z | ((uint64_t)cA.w << 32),
+                                (uint64_t)cB.x | ((uint64_t)cB.y << 32), (uint64_t)cB.z | ((uint64_t)cB.w << 32));
+                     ++pc;
+                 } while (lean_piece(blk) && --budget >= 0);
+             }
              if (blk >= nblk || budget < 0) break;
              pnext = pieces[pc < npieces ? pc : npieces - 1];
          }

@@ -168,6 +168,7 @@ struct phk_handle {
     double nonhom_frac = 0.0;  // share of the observation matrix that is het or missing (counted by pack_kernel)
     int mask_runs = 0;  // the rows hold runs of missing sites (pack_kernel: all-missing 8-site halves): KArgs::mask_runs
     int asm_run = 0;  // phk_set_asm_run; phk_create turns it on where the sequence exists (asm_run_kernels)
+    int fwd_run = 0;  // phk_set_fwd_run; the same for the forward kernel's run of lean pieces (fwd_run_kernels)
     int budget_num[3] = {1, 1, 1}, budget_den[3] = {1, 1, 1};  // phk_set_loop_budget_scale (tests): forward kernel, backward kernel, beta scan
     int poison = 0;  // diagnostic: fill the scratch buffers with this byte before every launch sequence (PHK_POISON=255: NaN patterns)
     std::vector<hipEvent_t> ev;  // triples (start, mid, end) per launch since the last timing query
@@ -203,6 +204,8 @@ bool pick_launchers(const phk_handle* h, Launchers* l) {
 
 // the handles whose sweeps have the hand-written block-run sequence (psmc_kernels.hip, PHK_ASM_RUN): K = 16, float32 kernels (R = 2 sweeps)
 bool asm_run_kernels(const phk_handle* h) { return h->K == 16 && !h->dbl; }
+// ... and those whose checkpointing forward kernel has one (PHK_FWD_RUN: R = 1, T = 8, NRM = 4; every other variant ignores the flag)
+bool fwd_run_kernels(const phk_handle* h) { return h->K == 16 && !h->dbl; }
 
 bool valid_R(int K, int R) { return R >= 1 && R <= 16 && (R & (R - 1)) == 0 && R <= K && K % R == 0 && K / R <= 16; }
 // Variants that are not compiled (launch.hip mirrors these rules).  float64 kernels whose lanes own many
@@ -837,6 +840,7 @@ phk::KArgs base_kargs(const phk_handle* h, const CallShape& c, int64_t b0, int64
     a.ops_f = a.ops_b = nullptr;  // slab_dense_ops sets them where the plan runs a one-state-per-lane kernel
     for (int i = 0; i < 4; ++i) a.loop_budget[i] = INT32_MAX;
     a.asm_run = 0;
+    a.fwd_run = h->fwd_run;
     a.scan_prio = 0;
     a.mask_runs = h->mask_runs;
     // the pre-folded blocks are laid out like the parameter blocks, five rows instead of seven
@@ -1005,6 +1009,10 @@ int phk_create(phk_handle** out, int K, const int8_t* data, int64_t N, int64_t L
 #if PHK_ASM_RUN
     h->asm_run = asm_run_kernels(h) ? 1 : 0;
     if (const char* env = std::getenv("PHK_ASM_RUN")) h->asm_run = (std::atoi(env) != 0 && asm_run_kernels(h)) ? 1 : 0;
+#endif
+#if PHK_FWD_RUN
+    h->fwd_run = fwd_run_kernels(h) ? PHK_FWD_RUN_DEFAULT : 0;
+    if (const char* env = std::getenv("PHK_FWD_RUN")) h->fwd_run = (std::atoi(env) != 0 && fwd_run_kernels(h)) ? 1 : 0;
 #endif
     if (h->risk.ensure(4 * sizeof(int)) != PHK_OK || hipMemset(h->risk.p, 0, 4 * sizeof(int)) != hipSuccess) {  // flag word + (kernel, sequence, block) of an overrun
         delete h;
@@ -1234,6 +1242,17 @@ int phk_set_asm_run(phk_handle* h, int on) {
 }
 
 int phk_get_asm_run(const phk_handle* h) { return h ? h->asm_run : 0; }
+
+int phk_set_fwd_run(phk_handle* h, int on) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+#if !PHK_FWD_RUN
+    if (on) return fail(PHK_EUNSUPPORTED, "this library was built without the forward kernel's hand-written run (-DPHK_FWD_RUN=0)");
+#endif
+    h->fwd_run = (on && fwd_run_kernels(h)) ? 1 : 0;  // (other kernels have no such sequence: the flag stays off)
+    return PHK_OK;
+}
+
+int phk_get_fwd_run(const phk_handle* h) { return h ? h->fwd_run : 0; }
 
 int phk_set_loop_budget_scale(phk_handle* h, int kernels, int num, int den) {
     if (!h) return fail(PHK_EINVAL, "handle is NULL");

@@ -296,6 +296,15 @@ constexpr float RATIO_MIN_EMIS0 = 0x1p-64f;
                        // PHK_ASM_RUN=0 in the environment).  Bit-identical to the C++ body (tests/test_asm_run_default.py); 0 builds a
                        // library without the sequence (EXTRA=-DPHK_ASM_RUN=0).  Timings: profiles/ab_asm_run.txt
 #endif
+#ifndef PHK_FWD_RUN
+#define PHK_FWD_RUN 1  // 1: fwd_kernel<float, 16, 1, 8, 4, true> runs its lean pieces, in waves of at most two observation rows whose sequences
+                       // fold, through the generated instruction sequence fwd_run_k16r1.inc (scripts/gen_fwd_asm.py) where the handle asks for
+                       // it (phk_set_fwd_run; PHK_FWD_RUN=0 in the environment selects the C++ body).  Bit-identical to the C++ body
+                       // (tests/test_fwd_run.py); 0 builds a library without the sequence (EXTRA=-DPHK_FWD_RUN=0).  Timings: profiles/ab_fwd_run.txt
+#endif
+#ifndef PHK_FWD_RUN_DEFAULT
+#define PHK_FWD_RUN_DEFAULT 1  // what a new K = 16 float32 handle starts with (profiles/ab_fwd_run.txt)
+#endif
 #ifndef PHK_FOLD_F64
 #define PHK_FOLD_F64 1  // A/B: 0 = the float64 kernels keep their emissions in the table (rounds 1-5); 1: folded like the float32 ones (round 6: cfg2 76 -> 67 ms)
 #endif
@@ -1082,6 +1091,8 @@ struct KArgs {
     int32_t scan_prio;  // s_setprio of the beta scan's waves (0..3)
     int32_t mask_runs;  // 1: the rows hold runs of missing sites; the one-state-per-lane kernels are launched in their *_mr form
     int32_t asm_run;  // 1: the K = 16, R = 2 float32 sweeps run their hot blocks through the hand-written sequence (0: the C++ body; tests)
+    int32_t fwd_run;  // 1: the K = 16, R = 1 float32 checkpointing forward kernel runs its lean pieces through its hand-written sequence
+                      // (takes the struct's tail padding: no other member moves)
 };
 
 // this sequence's pre-folded block (lane slice added by the caller), or null

@@ -136,6 +136,14 @@ class HipEngine:
         """The hand-written block-run sequence of the K = 16 float32 sweeps on / off (``phk_set_asm_run``; off = the C++ body)."""
         _lib.check(_lib.load().phk_set_asm_run(self._h, int(bool(on))))
 
+    def set_fwd_run(self, on: bool):
+        """The hand-written run of lean pieces of the K = 16 float32 forward kernel on / off (``phk_set_fwd_run``; off = the C++ body)."""
+        _lib.check(_lib.load().phk_set_fwd_run(self._h, int(bool(on))))
+
+    def get_fwd_run(self) -> bool:
+        """Whether the forward kernel of this handle uses that sequence (``phk_get_fwd_run``)."""
+        return bool(_lib.load().phk_get_fwd_run(self._h))
+
     def get_asm_run(self) -> bool:
         """Whether the sweeps of this handle use that sequence: the default for K = 16 float32 (``phk_get_asm_run``)."""
         return bool(_lib.load().phk_get_asm_run(self._h))
