@@ -233,6 +233,44 @@ int phk_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pst
                const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* weights,
                int64_t wstride_b, const int64_t* lens, double* ll, void* tract, void* stream);
 
+/* Bin moments (the reference has no counterpart): for every bin of scored sites of each sequence (b, s), the first two raw
+ * posterior moments of the bin sum S_k = sum_{t in bin} v(z_t) of a per-state value v -- the posterior mean of the sum and, as
+ * m2 - m1^2, its posterior variance, covariances between the bin's sites included: the per-site marginals determine the mean
+ * only.  Conventions of phk_tracts: z_0 ~ pi precedes site 0, alpha_t is the forward vector after site t with alpha_{-1} = pi,
+ * beta_{L-1} = 1 and beta_t holds the emissions of sites t+1 .. L-1 only, a missing site has e = 1, the W warm-up sites are
+ * conditioned on and not reported, and there is no warm-up correction.  Let v in [-1,1]^K be the particle's value row.  Bin k
+ * holds the scored sites s = W + k bin .. e = min(s + bin, L) - 1 (the last bin may be partial; nbin = ceil((L - W) / bin)), and
+ *   q1_e = 0,  q2_e = 0
+ *   w0 = e_{o_t} .* beta_t,   w1 = e_{o_t} .* q1_t,   w2 = e_{o_t} .* q2_t
+ *   beta_{t-1} = A w0
+ *   q1_{t-1}   = A (w1 + v .* w0)
+ *   q2_{t-1}   = A (w2 + 2 v .* w1 + v^2 .* w0)        for t = e, e-1, .., s
+ *   m1_k = sum_i alpha_{s-1}(i) q1_{s-1}(i) / sum_i alpha_{s-1}(i) beta_{s-1}(i) = E[ S_k | o ]
+ *   m2_k = sum_i alpha_{s-1}(i) q2_{s-1}(i) / (the same denominator)             = E[ S_k^2 | o ].
+ * (The third argument is formed as w2 + v .* (w1 + x1) with x1 the second.)
+ *   values     device double [B, K] with row stride vstride_b, or [K] with vstride_b = 0 (one row for all particles, like
+ *              `values` of phk_posterior); rounded to the handle's float type; values outside [-1, 1] are the caller's error
+ *              (|q1| <= n beta and q2 <= n^2 beta for a bin of n sites hold for values inside it only); centre and scale a
+ *              general row first and map the moments back (the variance is shift-invariant, and m2 - m1^2 of an uncentred row
+ *              cancels digits the float32 recursion does not have);
+ *   m1, m2     [B, S, nbin] double for both handle types (a float32 store of m2 would drop the digits m2 - m1^2 needs);
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N] or NULL: a site at or past its row's own length is stepped with v replaced by 0, so it adds
+ *              nothing; a bin without a site of the row's own is written as m1 = m2 = 0; an entry outside (W, L] is clamped and
+ *              raises the bad-index flag.
+ * q1 is signed, q2 is non-negative up to rounding; both run on beta's scale and take every power of two that rescales beta, so
+ * they need no exponent of their own.  v = 0 gives m1 = m2 = 0 exactly.  A bin whose denominator is not positive is written as
+ * 0 and raises the underflow flag (re-evaluate after phk_set_rescale_interval(h, 1)).  With W = L there is no scored site:
+ * nbin = 0, ll = 0, m1 and m2 are empty and may be NULL.
+ * params / prefold / inds / strides as phk_loglik_prefolded (prefold NULL: as phk_loglik).  Plan legs, slabs
+ * (phk_set_workspace_limit) and stream ordering are phk_posterior's, with the moment sweep in the decode sweep's place; the plan
+ * is read, never tuned or recorded; a hybrid plan runs as its serial half.  Every bin is written once, by one unit: the same bits
+ * for any slab and any order of the units.  Stream-ordered; no two calls on one handle may overlap.  PHK_EINVAL, before anything
+ * is enqueued, for a NULL handle, NULL params / inds / ll / values, bin < 1, W outside [0, L], NULL m1 or m2 with W < L. */
+int phk_bin_moments(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values,
+                    int64_t vstride_b, const int64_t* lens, double* ll, double* m1, double* m2, void* stream);
+
 /* Local likelihood-ratio scans (the reference has no counterpart): for every bin of scored sites of each sequence (b, s), the log
  * of the ratio
  *   P(o | the bin's sites are generated by an ALTERNATIVE model, the rest of the row by the fitted one) / P(o | fitted model),

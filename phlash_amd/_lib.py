@@ -33,6 +33,7 @@ SIGNATURES = {
     "phk_transitions": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp, _vp]),
     "phk_predictive": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "phk_tracts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "phk_bin_moments": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "phk_local_ratio": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
     "phk_pair_counts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "phk_viterbi": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),

@@ -34,7 +34,8 @@ namespace phk {
     hipError_t launch_loo_##tag(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st);     \
     hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_local_##tag(int T, int nrm, const KArgs& a, const RArgs& d, int units, int nt, hipStream_t st); \
-    hipError_t launch_pairs_##tag(int T, int nrm, const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_pairs_##tag(int T, int nrm, const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_moments_##tag(int T, int nrm, const KArgs& a, const MArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
@@ -1216,9 +1217,10 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
                                             "sample_back_kernel", "trans_kernel (serial sweep)", "trans_kernel (segment sweep)",
                                             "loo_kernel (serial sweep)", "loo_kernel (segment sweep)", "tract_kernel (serial sweep)",
                                             "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)",
-                                            "pairs_kernel (serial sweep)", "pairs_kernel (segment sweep)"};
+                                            "pairs_kernel (serial sweep)", "pairs_kernel (segment sweep)", "moments_kernel (serial sweep)",
+                                            "moments_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 19 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 21 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1696,7 +1698,7 @@ static int loglik_impl(phk_handle* h, const CallShape& c, void* grad, int grad_d
     return PHK_OK;
 }
 
-// The six sweeps that run_sweep runs in the gradient sweep's place.  Each entry point states its own argument checks, its own
+// The seven sweeps that run_sweep runs in the gradient sweep's place.  Each entry point states its own argument checks, its own
 // argument struct for the slab at (b0, s0) of the call's [B, S] outputs, and its launcher.
 
 int phk_posterior(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
@@ -1809,6 +1811,29 @@ int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_
         return PHK_PICK(local, h)(T, nrm, a, ra, units, 256, st);
     };
     return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("local-ratio", validate, 0, no_workspace, launch));
+}
+
+int phk_bin_moments(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                    const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const double* values, int64_t vstride_b,
+                    const int64_t* lens, double* ll, double* m1, double* m2, void* stream) {
+    const auto validate = [&] {
+        if (!values) return fail(PHK_EINVAL, "values must be a non-NULL device pointer (double [B, K] or [K])");
+        if (vstride_b < 0) return fail(PHK_EINVAL, "vstride_b must be >= 0");
+        if ((!m1 || !m2) && W < h->L) return fail(PHK_EINVAL, "m1 or m2 is NULL: both moments are written");
+        return (int)PHK_OK;
+    };
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        phk::MArgs ma;
+        ma.bin = bin;
+        ma.nbin = (h->L - W + bin - 1) / bin;
+        ma.lens = lens;
+        ma.values = values + b0 * vstride_b;
+        ma.vstride_b = vstride_b;
+        ma.m1 = m1 ? m1 + (b0 * S + s0) * ma.nbin : nullptr;
+        ma.m2 = m2 ? m2 + (b0 * S + s0) * ma.nbin : nullptr;
+        return PHK_PICK(moments, h)(T, nrm, a, ma, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("bin-moment", validate, 0, no_workspace, launch));
 }
 
 int phk_pair_counts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,

@@ -60,6 +60,17 @@ struct QArgs {
     void* tract;            // [B, S, nbin] real: E[prod of m(z_t) over the bin's own sites | o]
 };
 
+// bin moments (launch_moments.hip)
+struct MArgs {
+    int64_t bin;           // scored sites per bin (>= 1)
+    int64_t nbin;          // bins per sequence: ceil((Ltot - W) / bin)
+    const int64_t* lens;   // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    const double* values;  // [B, K] (row stride vstride_b) or [K] (vstride_b = 0): the per-state value v in [-1, 1]
+    int64_t vstride_b;
+    double* m1;            // [B, S, nbin]: E[S | o], S the sum of v(z_t) over the bin's own sites
+    double* m2;            // [B, S, nbin]: E[S^2 | o]
+};
+
 // local likelihood-ratio scans (launch_local.hip)
 struct RArgs {
     int64_t bin;           // scored sites per bin (>= 1)

@@ -8,7 +8,8 @@ from its Viterbi kernels (``PSMCKernel.viterbi`` -> ``phk_viterbi``) and its sam
 the leave-one-out check of the observations from its predictive sweep (``PSMCKernel.predictive`` -> ``phk_predictive``) and the
 tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``) and the local likelihood-ratio scans from its
 local-ratio sweep (``PSMCKernel.local_ratio`` -> ``phk_local_ratio``) and the expected transition matrix from its pair-count sweep
-(``PSMCKernel.pair_counts`` -> ``phk_pair_counts``); this module only builds the models, pads ragged inputs,
+(``PSMCKernel.pair_counts`` -> ``phk_pair_counts``) and the error band of the TMRCA track from its bin-moment sweep
+(``PSMCKernel.bin_moments`` -> ``phk_bin_moments``); this module only builds the models, pads ragged inputs,
 averages, counts and run-length encodes.  There is no CPU path.
 """
 
@@ -236,6 +237,76 @@ def tract_posterior(dms, data, t_max, t_min: float = 0.0, window_size: int = 100
     if spans is None:
         return track
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
+
+
+class TmrcaBand(NamedTuple):
+    """What ``tmrca_band`` returns: float64 tensors on the device for a matrix, lists with one tensor per contig for a list."""
+
+    mean: torch.Tensor  # [N, nbin]: the posterior mean of the bin-mean value, averaged over the models
+    sd: torch.Tensor  # [N, nbin]: its posterior standard deviation under the equal-weight mixture of the models
+    sd_within: torch.Tensor  # [N, nbin]: the part of sd from the unknown path (root of the mean of the per-model variances)
+    sd_between: torch.Tensor  # [N, nbin]: the part of sd from the unknown size history (sd of the per-model means)
+
+
+def tmrca_band(dms, data, window_size: int = 100, bin: int = 100, values=None, device=None, double_precision: bool = False):
+    """The track of ``posterior_tmrca`` with its error bar: per bin of ``bin`` windows, for every row of ``data``, the posterior
+    mean and standard deviation of the bin-MEAN value S / n, S = the sum over the bin's n windows of ``values``(z_t).  The
+    variance is exact (``PSMCKernel.bin_moments``) and holds the covariances between a bin's windows, which dominate it:
+    neighbouring windows share their TMRCA, so the per-window marginals would give far too narrow a band.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.  Raw moments
+        are linear in a mixture, so under the equal-weight mixture of the models the variance splits by the law of total
+        variance: ``sd_within``^2 = the mean of the per-model variances (the path is unknown), ``sd_between``^2 = the variance of
+        the per-model means (the size history is unknown), ``sd``^2 = their sum; ``mean`` = the mean of the per-model means.  All
+        four are formed from per-model means and variances in float64; no two large squares are subtracted.
+    data: int8 [N, L] het matrix of whole-contig rows (-1 missing, 0 hom, 1 het), or a list of ``RawContig`` (or of int8
+        matrices) of different lengths: they are padded with missing windows, and the padded windows add nothing (each row's own
+        length goes to the kernel, which masks them; a partial last bin is averaged over its own windows).
+    values: None for each model's ``eta.ect()`` (the TMRCA, in the model's own time unit), or [M] or [len(dms), M]: a value per
+        state, e.g. the indicator of a TMRCA range for the share of a bin's windows inside it.
+    Returns ``TmrcaBand(mean, sd, sd_within, sd_between)``: float64 [N, ceil(L / bin)] on the device for a matrix, lists of such
+    tensors (one per contig) for a list.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if values is None:
+        v = np.stack([np.asarray(torch.as_tensor(dm.eta.ect(), dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(M) for dm in dms])
+    else:
+        v = np.asarray(values.cpu() if isinstance(values, torch.Tensor) else values, dtype=np.float64)
+        assert v.shape in ((M,), (len(dms), M)), f"values: [{M}] or [{len(dms)}, {M}]"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    N, L = rows.shape
+    lens = np.full(N, L, dtype=np.int64)
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.bin_moments(pp, torch.arange(N, device=dev), values=v, bin=bin, lens=lens if spans is not None else None)
+    # the bin's own windows (at least 1 in every bin that is returned)
+    nbin = (L + bin - 1) // bin
+    n = np.clip(lens[:, None] - np.arange(nbin)[None, :] * bin, 1, bin).astype(np.float64)
+    n = torch.as_tensor(n, device=dev)
+    mu = out.mean / n  # [B, N, nbin]: per model
+    var = out.var / (n * n)
+    mean = mu.mean(0)
+    within = var.mean(0)
+    between = ((mu - mean) ** 2).mean(0)
+    tracks = (mean, torch.sqrt(within + between), torch.sqrt(within), torch.sqrt(between))
+    if spans is None:
+        return TmrcaBand(*tracks)
+    return TmrcaBand(*([t[r : r + k, : (length + bin - 1) // bin] for r, k, length in spans] for t in tracks))
 
 
 class LocalScan(NamedTuple):

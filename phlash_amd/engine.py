@@ -423,6 +423,32 @@ class HipEngine:
         _lib.check(rc)
         return ll, tract
 
+    def bin_moments(self, params: torch.Tensor, inds: torch.Tensor, values: torch.Tensor, warmup: int = 0, bin: int = 1,
+                    lens: torch.Tensor | None = None):
+        """Bin moments (``phk_bin_moments``): params / inds as ``run``.  ``values``: float64 [B, K] or [K] on the device, the
+        per-state value v in [-1, 1].  Returns (ll [B, S] float64, m1 [B, S, nbin] float64, m2 [B, S, nbin] float64) over bins of
+        ``bin`` scored sites (nbin = ceil((L - warmup) / bin)): per bin E[S | o] and E[S^2 | o] of S = the sum of v(z_t) over the
+        bin's sites, double for either handle type.  ``lens`` (int64 [N] on the device, one own length per data row of the
+        engine, ``warmup < len <= L``): a site at or past a row's own length adds nothing, a bin without a site of the row's own
+        is 0.  Padded states (K below the compiled size) get value 0 and have no mass."""
+        assert int(bin) >= 1 and 0 <= int(warmup) <= self.L
+        assert values.is_cuda and values.device == self.device and values.dtype == torch.float64, "values: float64 on the device"
+        assert values.shape in ((self.K_user,), (params.shape[0], self.K_user)), f"values: [K] or [B, K], got {tuple(values.shape)}"
+        c = self._sweep_call(params, inds, lens)
+        if c.pad_k:
+            values = torch.cat([values, torch.zeros(values.shape[:-1] + (c.pad_k,), dtype=values.dtype, device=values.device)], -1)
+        values = values.contiguous()
+        nbin = self._nbin(warmup, bin)
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        m1 = torch.empty((c.B, c.S, nbin), dtype=torch.float64, device=self.device)
+        m2 = torch.empty((c.B, c.S, nbin), dtype=torch.float64, device=self.device)
+        rc = _lib.load().phk_bin_moments(
+            *c.head, *c.grid, int(warmup), int(bin), values.data_ptr(), self.K if values.ndim == 2 else 0,
+            c.lens, ll.data_ptr(), m1.data_ptr() if nbin > 0 else None, m2.data_ptr() if nbin > 0 else None, c.stream,
+        )
+        _lib.check(rc)
+        return ll, m1, m2
+
     def local_ratio(self, params: torch.Tensor, alt: torch.Tensor, inds: torch.Tensor, warmup: int = 0, bin: int = 1,
                     lens: torch.Tensor | None = None):
         """Local likelihood-ratio scan (``phk_local_ratio``): params / inds as ``run``.  ``alt``: the alternative blocks,

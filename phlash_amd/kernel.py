@@ -92,6 +92,16 @@ class Tracts(NamedTuple):
     prob: torch.Tensor  # [..., nbin]: E[prod of weights(z_t) over the bin's sites | o]
 
 
+class BinMoments(NamedTuple):
+    """What ``PSMCKernel.bin_moments`` returns (float64 device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    mean: torch.Tensor  # [..., nbin]: E[sum of values(z_t) over the bin's own sites | o]
+    var: torch.Tensor  # [..., nbin]: the posterior variance of that sum
+    m1: torch.Tensor  # [..., nbin]: E[S | o] of the centred and scaled row the kernel ran on
+    m2: torch.Tensor  # [..., nbin]: E[S^2 | o] of the same row
+
+
 class LocalRatio(NamedTuple):
     """What ``PSMCKernel.local_ratio`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
 
@@ -375,6 +385,50 @@ class PSMCKernel:
             lens = self._lens_tensor(lens)
             ll, tract = _guarded(self, "tracts", pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
         return Tracts(self._strip(ll, added_B, added_S), self._strip(tract, added_B, added_S))
+
+    # ---- bin moments ----------------------------------------------------------------------------
+    def bin_moments(self, pp, index, *, values, bin: int = 1, lens=None) -> BinMoments:
+        """An error bar for a bin: the posterior mean and variance of S = the sum of ``values``(z_t) over the bin's sites, for
+        every bin of ``bin`` scored sites.  The variance is exact and holds the covariances between the bin's sites, which
+        dominate it: the per-site marginals give the mean only, and sampled paths only estimate the variance.  With ``values``
+        the states' expected coalescence times S / n is the bin's mean TMRCA and sqrt(var) / n its posterior standard deviation;
+        with an indicator of a set of states S is how many of the bin's sites have their state in the set.
+
+        ``values``: [M], or [B, M] with one row per particle of ``pp``, any real numbers.  Each particle's row is centred and
+        scaled before it goes to the kernel -- c_b = the mean of the row under the particle's own pi (for blocks per chunk: under
+        the sum of their pi rows), s_b = max |v - c_b|, the kernel runs on (v - c_b) / s_b in [-1, 1] (zeros where s_b = 0) -- and
+        the moments are mapped back in float64: ``mean`` = s m1 + c n and ``var`` = s^2 max(m2 - m1^2, 0), n the number of the
+        bin's own sites.  The variance does not depend on the centre, and m2 - m1^2 of a row far from its centre cancels digits
+        the float32 recursion does not have.  ``m1`` and ``m2`` are the raw moments of the row the kernel ran on.
+
+        Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as ``loglik``); nbin =
+        ceil((L - overlap) / bin).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <= L``):
+        a site at or past a row's own length adds nothing, and a bin without a site of the row's own is 0.  Returns
+        ``BinMoments(ll, mean, var, m1, m2)``, float64 device tensors for either ``float_type``; no gradient."""
+        with torch.no_grad():
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            B, S = pa.shape[0], inds.shape[0]
+            v = torch.as_tensor(np.array(values.cpu() if isinstance(values, torch.Tensor) else values, dtype=np.float64),
+                                dtype=torch.float64, device=self.device)
+            assert v.shape in ((self.M,), (B, self.M)), f"values: [{self.M}] or [{B}, {self.M}], got {tuple(v.shape)}"
+            assert bool(torch.isfinite(v).all()), "not all values finite"
+            v = v.expand(B, self.M)
+            # the centre as lo + (mean of v - lo): a row that is constant over the states is its own centre, exactly
+            pi = pa[:, :, 6, :].sum(1)  # [B, M]
+            lo = v.min(-1, keepdim=True).values
+            c = lo + ((v - lo) * pi).sum(-1, keepdim=True) / pi.sum(-1, keepdim=True)
+            s = (v - c).abs().max(-1, keepdim=True).values
+            vn = torch.where(s > 0, (v - c) / torch.where(s > 0, s, torch.ones_like(s)), torch.zeros_like(v)).clamp_(-1.0, 1.0).contiguous()
+            lens = self._lens_tensor(lens)
+            ll, m1, m2 = _guarded(self, "bin_moments", pa, inds, vn, warmup=self.overlap, bin=int(bin), lens=lens)
+            # the bin's own sites, counted from lens
+            own = (lens[inds] if lens is not None else torch.full((S,), self.L, dtype=torch.int64, device=self.device)) - self.overlap
+            start = torch.arange(m1.shape[-1], dtype=torch.int64, device=self.device) * int(bin)
+            n = (own[:, None] - start[None, :]).clamp_(0, int(bin)).to(torch.float64)  # [S, nbin]
+            mean = s[:, :, None] * m1 + c[:, :, None] * n[None]
+            var = s[:, :, None] ** 2 * (m2 - m1 * m1).clamp_(min=0.0)
+        strip = lambda x: self._strip(x, added_B, added_S)  # noqa: E731
+        return BinMoments(strip(ll), strip(mean), strip(var), strip(m1), strip(m2))
 
     # ---- local likelihood-ratio scans ------------------------------------------------------------
     def local_ratio(self, pp, alt, index, *, bin: int = 1, lens=None) -> LocalRatio:

@@ -11,6 +11,7 @@ The block loops of the decoding sweeps (K = 16 float32, T = 16, NRM = 4, segment
     python scripts/loop_report.py phlash_amd/csrc/build/launch_loo_f32_16.o loo_kernelIfLi16ELi4ELi16ELi4ELb1 4000
     python scripts/loop_report.py phlash_amd/csrc/build/launch_tract_f32_16.o tract_kernelIfLi16ELi4ELi16ELi4ELb1 3000
     python scripts/loop_report.py phlash_amd/csrc/build/launch_local_f32_16.o local_kernelIfLi16ELi4ELi16ELi4ELb1 4000
+    python scripts/loop_report.py phlash_amd/csrc/build/launch_moments_f32_16.o moments_kernelIfLi16ELi4ELi16ELi4ELb1 4000
 
 The 16-site block loop of the posterior predictive simulator (float64, K at run time; rows + statistics, rows, statistics):
 
