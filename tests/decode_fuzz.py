@@ -112,7 +112,7 @@ class Draw(types.SimpleNamespace):
         return s + f" lens={None if self.lens is None else self.lens.tolist()}"
 
 
-STREAMS = {"posterior": 0, "viterbi": 1, "transitions": 2, "predictive": 3, "tracts": 4, "local": 5, "pairs": 6}  # a random stream per kind
+STREAMS = {"posterior": 0, "viterbi": 1, "transitions": 2, "predictive": 3, "tracts": 4, "local": 5, "pairs": 6, "moments": 7}  # a random stream per kind
 
 
 def _draw(seed, kind, force_dbl, with_rng=False):
