@@ -1340,7 +1340,8 @@ constexpr int bwd_waves_per_simd() {
 template <typename real, int K, int R, int T, int NRM>
 constexpr bool sweep_folds() { return PHK_SWEEP_FOLD != 0 && (sizeof(real) == 4 || PHK_FOLD_F64 != 0) && PHK_SWEEP_V2 != 0 && NRM > 1 && T == 8 && T * (K / R) * (int)sizeof(real) <= 256; }
 #ifndef PHK_PARK_HREG
-#define PHK_PARK_HREG 2  // ... of the folded bodies with PHK_HET_REGS: 68 floats of LDS per thread = 69,632 B per 256-thread workgroup, two
+#define PHK_PARK_HREG 2  // ... of the folded bodies with PHK_HET_REGS: 68 floats of LDS per thread = 69,632 B per 256-thread workgroup (76 floats
+                         // = 77,824 B where the hand-written block run adds its kept vector: sweep_run_kept), two
                          // workgroups per CU (the launcher raises the kernel's dynamic-LDS limit: launch.hip, bwd_rtn).  Every parked
                          // vector costs ~0.25 ms of cfg2's backward phase (1 / 2 / 3 / 5 parked: spills in the block loop / 19.2 / 19.4 /
                          // 20.9 ms, profiles/r06_ab_experiments.txt item 2); 2 is the fewest that keeps the block loop out of scratch
@@ -1356,12 +1357,18 @@ constexpr int sweep_parked() {
     if (!(PHK_SWEEP_V2 != 0 && NRM > 1 && T == 8 && (K / R) * (int)sizeof(real) == 32)) return 0;
     return sweep_folds<real, K, R, T, NRM>() ? (PHK_HET_REGS == 2 ? PHK_PARK_HREG2 : PHK_HET_REGS != 0 ? PHK_PARK_HREG : PHK_PARK) : PHK_PARK_UNFOLDED;
 }
-// reals per thread of the backward kernel's LDS slice: emission table + mass rows + parked vectors, the stride in 16-byte
-// units odd (the 16 lanes of a ds_read_b128 group then fall on 16 different bank quads, see Lane::ETAB_STRIDE)
+// reals at the end of the slice that only the hand-written block run of the K = 16, R = 2 float32 sweeps touches (sweep_run_k16r2.inc,
+// scripts/gen_sweep_asm.py: an all-hom block keeps suf(v.*w) of one more site there between its two passes); the C++ bodies leave them alone
+template <typename real, int K, int R, int T, int NRM>
+constexpr int sweep_run_kept() {
+    return (PHK_ASM_RUN != 0 && sizeof(real) == 4 && K == 16 && R == 2 && sweep_folds<real, K, R, T, NRM>() && PHK_HET_REGS == 1) ? 2 * Lane<real, K, R>::NP : 0;
+}
+// reals per thread of the backward kernel's LDS slice: emission table + mass rows + parked vectors (+ the block run's kept vector), the
+// stride in 16-byte units odd (the 16 lanes of a ds_read_b128 group then fall on 16 different bank quads, see Lane::ETAB_STRIDE)
 template <typename real, int K, int R, int T, int NRM>
 constexpr int sweep_lds_stride() {
     using L = Lane<real, K, R>;
-    constexpr int park = sweep_parked<real, K, R, T, NRM>() * 2 * L::NP;
+    constexpr int park = sweep_parked<real, K, R, T, NRM>() * 2 * L::NP + sweep_run_kept<real, K, R, T, NRM>();
     constexpr int gtab = (sweep_folds<real, K, R, T, NRM>() && PHK_HET_REGS != 2) ? 3 * L::EROW : 0;
     if (park + gtab == 0) return L::ETAB_STRIDE;
     constexpr int per16 = 16 / (int)sizeof(real);
@@ -1725,9 +1732,11 @@ __global__ __launch_bounds__(NT_MAX, (bwd_waves_per_simd<real, K, R, T, SEG>()))
             // register plan -- what the compiler cannot do at the join of two C++ bodies.  Same arithmetic, operation for
             // operation; waves that hold more than two observation rows keep the C++ loop.
             if constexpr (HREG && !HREG2 && sizeof(real) == 4 && K == 16 && R == 2) {
-                // (an all-hom block of the sequence parks two w vectors where the loop below parks its own: the offsets are the generator's)
-                static_assert(L::ETAB_STRIDE == 28 && L::EROW == 8 && PARKN == 2 && sweep_lds_stride<real, K, R, T, NRM>() == 68,
-                              "sweep_run_k16r2.inc: the thread's LDS slice is table 28 + mass rows 24 + parked 16 floats");
+                // (an all-hom block of the sequence parks two w vectors where the loop below parks its own, and keeps one suf(v.*w)
+                // vector in the eight floats behind them, which the loop below never touches: the offsets are the generator's)
+                static_assert(L::ETAB_STRIDE == 28 && L::EROW == 8 && PARKN == 2 && sweep_run_kept<real, K, R, T, NRM>() == 8 &&
+                                  sweep_lds_stride<real, K, R, T, NRM>() == 76,
+                              "sweep_run_k16r2.inc: the thread's LDS slice is table 28 + mass rows 24 + parked 16 + kept 8 floats");
                 if (A.asm_run != 0 && two_rows && blk >= stop) {
                     // (the statement's scalar operands must be SGPRs to the compiler's divergence analysis, which cannot see that
                     // `stop` -- it depends on whether this unit owns a partial-sum slot -- is the same in every lane)

@@ -14,7 +14,15 @@ scans_adj, suffix_vw, beta_prev, carry with the SPLIT layout at R = 2): every fm
 uses is one instruction here with the same operands in the same order, so the results are bit-identical
 (tests/test_asm_run_default.py, tests/test_hip_parity.py::test_asm_block_run_equals_the_cxx_body).  What is NOT repeated is
 suf(v.*w) of a site where the forward pass can still find the beta pass's copy in registers (the same instructions on the same
-inputs: the same bits): six of the eight sites of an all-hom block, three of a mixed one (see SAVED_HOM / SAVED_MIXED in build()).
+inputs: the same bits): seven of the eight sites of an all-hom block (six in registers, one in the thread's LDS slice), three of a
+mixed one (see SAVED_HOM / LDS_KEPT / SAVED_MIXED in build()).  Nor are the adds of a zero: where the C++ source adds a carry or a
+first term to a zero-initialised scan entry (svw3 = 0 + cv; 0 + a3; the last entries of pre, suf and svw), `Gen.seed()` hands out the
+source register instead of `v_pk_add_f32 d, x, 0`.  Every such x is a product or a sum of non-negative numbers -- never -0 -- and
+the kernels keep float32 denormals, so x + 0 has the bits of x.  All of them went (per site one in the beta pass -- its carry lands
+where svw3 was, the chain's total in a register of the site's result that is dead until then -- and three in the forward pass, four
+where the site's vector is computed again).  Kept: none.  `seed(keep=True)` still emits the add, for an entry that would be overwritten
+in place while its source must survive, and nothing needs it: the one chain that is updated in place and starts from such a seed
+(suf(a): Y0 = a3, then Y0 + ca) reads a3 and writes the chain's own register.
 
     python scripts/gen_sweep_asm.py [out.inc]     write the sequence (the Makefile's rule) and print the counts below
     python scripts/gen_sweep_asm.py --report      only print, per kind of block, the instructions of one trip through the loop
@@ -44,6 +52,7 @@ class Gen:
         self.ins = []       # (text, defs, uses, kind)
         self.next_free = TBASE
         self.labels = 0
+        self.seeds_aliased = 0  # scan seeds read from their source register instead of through an x + 0 (seed())
 
     # ---- register helpers ------------------------------------------------------------------------------------------------
     def pair(self):
@@ -129,6 +138,17 @@ class Gen:
             self.emit(f"v_pk_add_f32 {self.txt(d)}, {self.txt(a)}, 0 op_sel_hi:[1,0]", [d], [a], "pk")
         else:
             self.emit(f"v_pk_add_f32 {self.txt(d)}, {self.txt(a)}, {self.txt(b)}", [d], [a, b], "pk")
+
+    def seed(self, d, x, keep=False):
+        """The entry of a scan that the C++ source writes as 0 + x (a carry, or the first term, added to a zero-initialised entry).
+        Returns the register to read for it: x itself -- every x here is a product or a sum of non-negative numbers, never -0,
+        and the kernels run with float32 denormals on, so x + 0 has the bits of x and the add is not emitted -- or, with `keep`,
+        d after `v_pk_add_f32 d, x, 0` (for an entry that is later overwritten in place while x must survive)."""
+        if keep:
+            self.pk_add(d, x, None)
+            return d
+        self.seeds_aliased += 1
+        return x
 
     def lane_total(self, d, x):
         """(x.lo + x.hi, x.hi + x.lo)"""
@@ -361,21 +381,40 @@ def build():
     SAVED_HOM = {1: Tt, 2: [ADDR, FXP, LTZ, CZ], 3: TAIL, 4: R[6], 5: R[7]}
     SAVED_MIXED = {1: Tt, 2: [ADDR, FXP, LTZ, CZ]}
     PARK_BYTE = (28 + 24) * 4  # the slice: emission table (Lane::ETAB_STRIDE = 28 floats), three mass rows, the parked vectors
-    PARKED = {6: PARK_BYTE, 7: PARK_BYTE + 32}  # R[j] -> byte offset in the slice (sweep_lds_stride: 68 floats = 272 bytes)
+    PARKED = {6: PARK_BYTE, 7: PARK_BYTE + 32}  # R[j] -> byte offset in the slice
+    #   LDS_KEPT     an all-hom block also keeps the vector of site 6, for which no register is left: the beta pass computes it in the
+    #                Z chain's own registers (two quads) and writes it to the eight floats of the slice behind the parked vectors
+    #                (psmc_kernels.hip, sweep_run_kept: the C++ bodies never touch them); the forward pass asks it back into Tt as soon
+    #                as site 1 has used the vector kept there, five sites before it is read, and the waits for the parked w vectors
+    #                of sites 5 and 6 cover it (a wave's LDS accesses complete in order).  Site 7 is the one site whose vector is
+    #                still computed twice: the slice has four floats left, a vector is eight.
+    SLICE_FLOATS = 76  # sweep_lds_stride of these kernels: 19 units of 16 bytes, odd -- no bank conflict among the lanes of a ds_read_b128
+    KEEP_BYTE = PARK_BYTE + 64
+    LDS_KEPT = {6: (KEEP_BYTE, Tt, 1)}  # site -> (byte offset, the four pairs it comes back to, the site that frees them)
+    assert KEEP_BYTE + 32 <= SLICE_FLOATS * 4 and Tt[0][1] % 4 == 0 and ZQ[0][1] % 4 == 0
 
     def park(j, store):
         for q in range(2):
             quad = ("q", R[j][2 * q][1])
             off = PARKED[j] + 16 * q
-            assert off + 16 <= 68 * 4
+            assert off + 16 <= KEEP_BYTE
             if store:
                 g.emit(f"ds_write_b128 {LDS}, {g.txt(quad)} offset:{off}", [], [LDS, quad], "lds")
             else:
                 g.emit(f"ds_read_b128 {g.txt(quad)}, {LDS} offset:{off}", [quad], [LDS], "lds")
 
+    def keep(i, store):
+        off, back, _ = LDS_KEPT[i]
+        for q in range(2):
+            if store:  # (ZC[0..3] are the two quads of the Z chain, in this order)
+                g.emit(f"ds_write_b128 {LDS}, {g.txt(ZQ[q])} offset:{off + 16 * q}", [], [LDS, ZQ[q]], "lds")
+            else:
+                quad = ("q", back[2 * q][1])
+                g.emit(f"ds_read_b128 {g.txt(quad)}, {LDS} offset:{off + 16 * q}", [quad], [LDS], "lds")
+
     def beta_site(i, tests, ZC):
         """ZC: the four pairs of the site's Z chain (the chain's own registers, or a SAVED set)"""
-        LTZ, CZ = LTY, CY
+        LTZ = LTY
         Wi = W(i)
         Bn = R[i]
         if tests:
@@ -394,19 +433,22 @@ def build():
         g.pk_fma(XC[1], Pb[1], Wi[1], XC[0])
         g.pk_fma(ZC[2], Pv[1], Wi[1], ZC[1])
         g.pk_fma(XC[2], Pb[2], Wi[2], XC[1])
-        g.pk_fma(ZC[3], Pv[0], Wi[0], ZC[2])   # tv
+        # (tv goes to a register of the site's result, dead until the site's last instructions write it: the carry can then land
+        # in ZC[3] itself, which is where svw3 = 0 + cv is read)
+        TV = Bn[3]
+        g.pk_fma(TV, Pv[0], Wi[0], ZC[2])      # tv
         g.pk_fma(XC[3], Pb[3], Wi[3], XC[2])   # tb
-        g.lane_total(LTZ, ZC[3])
+        g.lane_total(LTZ, TV)
         g.lane_total(LTX, XC[3])
         # nb_h = fma(d_h, w_h, pbw_h): pbw = (0, X0, X1, X2)  (independent work between the totals and the DPP reads)
         g.pk_fma(YC[0], Pd[0], Wi[0], None)
         g.pk_fma(YC[1], Pd[1], Wi[1], XC[0])
         g.pk_fma(YC[2], Pd[2], Wi[2], XC[1])
         g.pk_fma(YC[3], Pd[3], Wi[3], XC[2])
-        g.carry(CZ, LTZ, ZC[3], DN1, prefix=False)   # cv
+        g.carry(ZC[3], LTZ, TV, DN1, prefix=False)   # cv
         g.carry(CX, LTX, XC[3], UP1, prefix=True)    # cb
         # svw_h += cv: svw = (Z2, Z1, Z0, 0)
-        g.pk_add(ZC[3], CZ, None)        # svw3 = 0 + cv   (the C++ source: splat(0) + cv)
+        CZ = g.seed(None, ZC[3])         # svw3 = 0 + cv   (the C++ source: splat(0) + cv)
         g.pk_add(ZC[0], ZC[0], CZ)       # svw2
         g.pk_add(ZC[1], ZC[1], CZ)       # svw1
         g.pk_add(ZC[2], ZC[2], CZ)       # svw0
@@ -429,10 +471,10 @@ def build():
             # the chains of u.*a and a alone; the site's gu and gd rows need no scan of this pass and fill the chains' gaps
             svw = [kept[2], kept[1], kept[0], kept[3]]
             g.pk_fma(XC[0], Pu[0], a[0], None)
-            g.pk_add(YC[0], a[3], None)            # 0 + a3
+            Y0 = g.seed(YC[0], a[3])               # 0 + a3
             g.pk_fma(GU[0], a[0], svw[0], GU[0])
             g.pk_fma(XC[1], Pu[1], a[1], XC[0])
-            g.pk_add(YC[1], YC[0], a[2])
+            g.pk_add(YC[1], Y0, a[2])
             g.pk_fma(GU[1], a[1], svw[1], GU[1])
             g.pk_fma(XC[2], Pu[2], a[2], XC[1])
             g.pk_add(YC[2], YC[1], a[1])
@@ -448,10 +490,10 @@ def build():
                 park(refill, store=False)
         else:
             g.pk_fma(XC[0], Pu[0], a[0], None)
-            g.pk_add(YC[0], a[3], None)            # 0 + a3
+            Y0 = g.seed(YC[0], a[3])               # 0 + a3
             g.pk_fma(ZC[0], Pv[3], Wi[3], None)
             g.pk_fma(XC[1], Pu[1], a[1], XC[0])
-            g.pk_add(YC[1], YC[0], a[2])
+            g.pk_add(YC[1], Y0, a[2])
             g.pk_fma(ZC[1], Pv[2], Wi[2], ZC[0])
             g.pk_fma(XC[2], Pu[2], a[2], XC[1])
             g.pk_add(YC[2], YC[1], a[1])
@@ -470,23 +512,26 @@ def build():
         if kept is None:
             g.carry(CZ, LTZ, ZC[3], DN1, prefix=False)    # cv
         # pre = (0, X0, X1, X2) + cu ; suf = (Y2, Y1, Y0, 0) + ca ; svw = (Z2, Z1, Z0, 0) + cv
-        g.pk_add(XC[3], CX, None)
-        g.pk_add(YC[3], CY, None)
+        # (the three 0 + carry entries are the carries themselves, read where they stand: nothing writes cu, ca, cv before the next
+        # site's carries, behind every read of this site;  Y0 + ca reads a3, which the site's last instructions still need, and
+        # writes the chain's own register)
+        X3 = g.seed(XC[3], CX)
+        Y3 = g.seed(YC[3], CY)
         if kept is None:
-            g.pk_add(ZC[3], CZ, None)
+            Z3 = g.seed(ZC[3], CZ)
         for k in range(3):
             g.pk_add(XC[k], XC[k], CX)
-            g.pk_add(YC[k], YC[k], CY)
+            g.pk_add(YC[k], Y0 if k == 0 else YC[k], CY)
             if kept is None:
                 g.pk_add(ZC[k], ZC[k], CZ)
-        pre = [XC[3], XC[0], XC[1], XC[2]]
-        suf = [YC[2], YC[1], YC[0], YC[3]]
+        pre = [X3, XC[0], XC[1], XC[2]]
+        suf = [YC[2], YC[1], YC[0], Y3]
         for h in range(NP):
             g.pk_fma(GB[h], Wi[h], suf[h], GB[h])
         for h in range(NP):
             g.pk_fma(GV[h], Wi[h], pre[h], GV[h])
         if kept is None:
-            svw = [ZC[2], ZC[1], ZC[0], ZC[3]]
+            svw = [ZC[2], ZC[1], ZC[0], Z3]
             for h in range(NP):
                 g.pk_fma(GU[h], a[h], svw[h], GU[h])
         if last and not tests:
@@ -512,12 +557,23 @@ def build():
             beta_site(i, tests, saved.get(i, ZC))
             if parks and i + 1 in PARKED:  # w of site i (R[i + 1]) has just been read for the last time in this pass
                 park(i + 1, store=True)
+            if parks and i in LDS_KEPT:    # the site's vector stands in the Z chain, which the next sites of this pass leave alone
+                assert all(j in saved for j in range(1, i))
+                keep(i, store=True)
         a = A
         for i in range(T):
             t = ZC if i == 0 else R[i]
+            kept = ZC if i == 0 else saved.get(i)
+            if parks and i in LDS_KEPT:
+                kept = LDS_KEPT[i][1]
             # (site i's kept vector sits in R[i + 2], the registers of w of site i + 1: asked back as soon as the vector is used)
-            fwd_site(i, tests, a, t, ZC if i == 0 else saved.get(i), refill=i + 2 if parks and i + 2 in PARKED else None,
-                     wait=parks and i + 1 in PARKED)
+            fwd_site(i, tests, a, t, kept, refill=i + 2 if parks and i + 2 in PARKED else None, wait=parks and i + 1 in PARKED)
+            if parks:
+                for j, (_, back, free) in LDS_KEPT.items():
+                    if free == i:
+                        # (a site between the two waits for its parked w: that wait is the one that covers this read)
+                        assert back is saved[i] and any(n + 1 in PARKED for n in range(i + 1, j))
+                        keep(j, store=False)
             a = t
         # (the block's result, beta at its left edge, stays in R[0]: see the run's prologue)
 
@@ -612,7 +668,7 @@ def build():
         g.emit(f"v_mov_b32_e32 {AN[i]}, {g.txt(quad_lane(PQ0, i))}", [AN[i]], [quad_lane(PQ0, i)])
         g.emit(f"v_mov_b32_e32 {AN[4 + i]}, {g.txt(quad_lane(PQ1, i))}", [AN[4 + i]], [quad_lane(PQ1, i)])
     lines, nops = g.finish()
-    return lines, nops, g.next_free
+    return lines, nops, g.next_free, {"slice_floats": SLICE_FLOATS, "seeds_aliased": g.seeds_aliased}
 
 
 def path_counts(lines):
@@ -651,9 +707,10 @@ def path_counts(lines):
 
 
 def main():
-    lines, nops, top = build()
+    lines, nops, top, info = build()
     for name, c in path_counts(lines).items():
         print(f"{name} block: " + ", ".join(f"{k} {v}" for k, v in c.items()))
+    print(f"LDS slice: {info['slice_floats']} floats per thread; scan seeds read in place (no x + 0): {info['seeds_aliased']} in the two bodies")
     if len(sys.argv) > 1 and sys.argv[1] == "--report":
         return
     out = sys.argv[1] if len(sys.argv) > 1 else "phlash_amd/csrc/sweep_run_k16r2.inc"
