@@ -158,8 +158,19 @@ __global__ __launch_bounds__(NT_MAX, (sweep_waves_per_simd<real>(T))) void decod
                     V p[NP];
 #pragma unroll
                     for (int h = 0; h < NP; ++h) p[h] = al[i][h] * beta[h];
-                    const real z = lane.total(p);
+                    real z = lane.total(p);
                     risky = risky || !(z > real(0));
+                    // (a model with massless states: beta is scaled by its total over ALL states, and the live states' share of
+                    // it can fall below 1 / FLT_MAX -- dead states that explain the hets better, 1e6 per het for a lone live
+                    // state 0 -- so that z > 0 and 1 / z = inf: gamma came back as inf and NaN with the flag clear,
+                    // tests/test_massless_fuzz.py.  Such a z, subnormal ones included, is scaled up first, with its products.)
+                    constexpr real Z_TINY = sizeof(real) == 4 ? real(0x1p-100) : real(0x1p-900);
+                    if (__builtin_expect(z < Z_TINY, 0)) {
+                        const V up = splat<real>(sizeof(real) == 4 ? real(0x1p64) : real(0x1p200));
+#pragma unroll
+                        for (int h = 0; h < NP; ++h) p[h] = p[h] * up;
+                        z = z * up[0];
+                    }
                     const V iz = splat<real>(z > real(0) ? real(1) / z : real(0));
 #pragma unroll
                     for (int h = 0; h < NP; ++h) acc[h] = fma2<real>(p[h], iz, acc[h]);

@@ -146,6 +146,13 @@ template <typename real, int R>
 struct Group {
     real up1, up2, up3;  // 1.0 where rank >= n, else 0.0   (shifts by 4 and 8 are masked by DPP itself)
     real dn1, dn2, dn3;  // 1.0 where rank + n < R, else 0.0
+    // The same as bit masks (all ones / 0), for the reads that cross into ANOTHER sequence's lanes (row_shr / row_shl at R = 2
+    // and R = 8: lane 0 of a group reads the last lane of the group before it).  Those were multiplied by up / dn until a
+    // neighbour's value was inf or NaN -- a gradient that float32 cannot hold, e.g. of a model whose one live state is the last
+    // -- and inf * 0 = NaN went into every sequence of the 16-lane row (tests/test_massless_fuzz.py).  x & ones = x, x & 0 = +0:
+    // the bits of x * 1 and, up to the sign of a zero, of x * 0 for every finite x.  (The quad_perm reads of R = 4 stay inside
+    // the group.)
+    uint32_t upm1, upm2, dnm1, dnm2;
 
     __device__ __forceinline__ void init(int rank) {
         up1 = rank >= 1 ? real(1) : real(0);
@@ -154,6 +161,16 @@ struct Group {
         dn1 = rank + 1 < R ? real(1) : real(0);
         dn2 = rank + 2 < R ? real(1) : real(0);
         dn3 = rank + 3 < R ? real(1) : real(0);
+        upm1 = rank >= 1 ? ~0u : 0u;
+        upm2 = rank >= 2 ? ~0u : 0u;
+        dnm1 = rank + 1 < R ? ~0u : 0u;
+        dnm2 = rank + 2 < R ? ~0u : 0u;
+    }
+    static __device__ __forceinline__ float keep(float x, uint32_t m) {
+        return __builtin_bit_cast(float, __builtin_bit_cast(uint32_t, x) & m);
+    }
+    static __device__ __forceinline__ double keep(double x, uint32_t m) {
+        return __builtin_bit_cast(double, __builtin_bit_cast(uint64_t, x) & (((uint64_t)m << 32) | m));
     }
 
     // all-reduce: every lane of the group gets the same bits (each step adds a commutative pair)
@@ -173,15 +190,15 @@ struct Group {
         if constexpr (R == 1) {
             return real(0);
         } else if constexpr (R == 2) {
-            return dpp_<ROW_SHR(1)>(x) * up1;
+            return keep(dpp_<ROW_SHR(1)>(x), upm1);
         } else if constexpr (R == 4) {
             real y = dpp_<QP(0, 0, 1, 2)>(x) * up1;
             y = fma_(dpp_<QP(0, 0, 0, 1)>(x), up2, y);
             return fma_(dpp_<QP(0, 0, 0, 0)>(x), up3, y);
         } else if constexpr (R == 8) {
-            real y = dpp_<ROW_SHR(1)>(x) * up1;
-            y = fma_(dpp_<ROW_SHR(1)>(y), up1, y);
-            y = fma_(dpp_<ROW_SHR(2)>(y), up2, y);
+            real y = keep(dpp_<ROW_SHR(1)>(x), upm1);
+            y = keep(dpp_<ROW_SHR(1)>(y), upm1) + y;  // (one rounding, as the fused multiply by 1.0 had)
+            y = keep(dpp_<ROW_SHR(2)>(y), upm2) + y;
             return y + dpp_<ROW_SHR(4), 0xA>(y);
         } else {
             real y = dpp_<ROW_SHR(1)>(x);
@@ -196,15 +213,15 @@ struct Group {
         if constexpr (R == 1) {
             return real(0);
         } else if constexpr (R == 2) {
-            return dpp_<ROW_SHL(1)>(x) * dn1;
+            return keep(dpp_<ROW_SHL(1)>(x), dnm1);
         } else if constexpr (R == 4) {
             real y = dpp_<QP(1, 2, 3, 3)>(x) * dn1;
             y = fma_(dpp_<QP(2, 3, 3, 3)>(x), dn2, y);
             return fma_(dpp_<QP(3, 3, 3, 3)>(x), dn3, y);
         } else if constexpr (R == 8) {
-            real y = dpp_<ROW_SHL(1)>(x) * dn1;
-            y = fma_(dpp_<ROW_SHL(1)>(y), dn1, y);
-            y = fma_(dpp_<ROW_SHL(2)>(y), dn2, y);
+            real y = keep(dpp_<ROW_SHL(1)>(x), dnm1);
+            y = keep(dpp_<ROW_SHL(1)>(y), dnm1) + y;
+            y = keep(dpp_<ROW_SHL(2)>(y), dnm2) + y;
             return y + dpp_<ROW_SHL(4), 0x5>(y);
         } else {
             real y = dpp_<ROW_SHL(1)>(x);

@@ -155,14 +155,15 @@ class Gen:
         self.emit(f"v_pk_add_f32 {self.txt(d)}, {self.txt(x)}, {self.txt(x)} op_sel:[0,1] op_sel_hi:[1,0]", [d], [x], "pk")
 
     def carry(self, dst, lt, tot, mask, prefix):
-        """Lane::carry at R = 2.  prefix: c = row_shr:1(lane total) * up1, r = (c, c + tot.lo);  suffix: c = row_shl:1(...) * dn1,
-        r = (c + tot.hi, c).  lt: pair holding the lane total in its low half."""
+        """Lane::carry at R = 2.  prefix: c = row_shr:1(lane total) & upm1, r = (c, c + tot.lo);  suffix: c = row_shl:1(...) & dnm1,
+        r = (c + tot.hi, c).  lt: pair holding the lane total in its low half.  (A bit mask, not a multiply by 0 / 1: the lane read
+        belongs to another sequence at the group's edge, and its inf or NaN times 0 would be NaN here: Group in psmc_kernels.hip.)"""
         if prefix:
-            self.emit(f"v_mul_f32_dpp {self.txt(self.lo(dst))}, {self.txt(self.lo(lt))}, {self.txt(mask)} row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1",
+            self.emit(f"v_and_b32_dpp {self.txt(self.lo(dst))}, {self.txt(self.lo(lt))}, {self.txt(mask)} row_shr:1 row_mask:0xf bank_mask:0xf bound_ctrl:1",
                       [self.lo(dst)], [self.lo(lt), mask], "dpp")
             self.emit(f"v_add_f32_e32 {self.txt(self.hi(dst))}, {self.txt(self.lo(tot))}, {self.txt(self.lo(dst))}", [self.hi(dst)], [self.lo(tot), self.lo(dst)])
         else:
-            self.emit(f"v_mul_f32_dpp {self.txt(self.hi(dst))}, {self.txt(self.lo(lt))}, {self.txt(mask)} row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1",
+            self.emit(f"v_and_b32_dpp {self.txt(self.hi(dst))}, {self.txt(self.lo(lt))}, {self.txt(mask)} row_shl:1 row_mask:0xf bank_mask:0xf bound_ctrl:1",
                       [self.hi(dst)], [self.lo(lt), mask], "dpp")
             self.emit(f"v_add_f32_e32 {self.txt(self.lo(dst))}, {self.txt(self.hi(tot))}, {self.txt(self.hi(dst))}", [self.lo(dst)], [self.hi(tot), self.hi(dst)])
 
@@ -723,7 +724,7 @@ def main():
     ops_in = []
     for nm, var in (("pb", "lane.b"), ("pd", "lane.d"), ("pu", "lane.u"), ("pv", "lane.v"), ("rh", "rhet")):
         ops_in += [f'[{nm}{h}] "v"({var}[{h}])' for h in range(NP)]
-    ops_in += ['[up1] "v"(lane.g.up1)', '[dn1] "v"(lane.g.dn1)', '[words] "v"(asm_words)', '[lds] "v"(asm_lds)', '[stop] "s"(asm_stop)',
+    ops_in += ['[up1] "v"(lane.g.upm1)', '[dn1] "v"(lane.g.dnm1)', '[words] "v"(asm_words)', '[lds] "v"(asm_lds)', '[stop] "s"(asm_stop)',
                '[blklo] "s"(asm_blklo)', '[ckstep] "s"(asm_ckstep)', '[ebstep] "s"(asm_ebstep)', '[ckpiece] "s"(asm_ckpiece)']
     clob = [f'"v{i}"' for i in range(TBASE, 256)] + [f'"s{i}"' for i in range(86, 100)] + ['"vcc"', '"scc"', '"memory"']
     with open(out, "w") as f:
