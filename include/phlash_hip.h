@@ -400,6 +400,51 @@ int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64
                      const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, double* ll,
                      uint8_t* paths, int64_t path_stride, void* stream);
 
+/* Sampled tract spectra (the reference has no counterpart): the paths of phk_sample_paths reduced inside the kernel to what is
+ * not additive over sites -- how many tracts a row has, how long they are, which bins lie in a long one -- without a byte of
+ * path stored.  Conventions of phk_sample_paths: params / prefold / inds / strides, W, n_samples, seed, and q = b * S + s the
+ * position in THIS CALL.
+ *   draws        sample r of sequence q is, byte for byte, the path phk_sample_paths returns for (seed, q, r) on the same handle
+ *                and plan: the same forward leg and alpha checkpoints, the same draw, the same Philox counters, the same folded
+ *                factors and rescale schedule.
+ *   the set      masks: device uint64 [B] (mask_stride = 1, one per particle) or [1] (mask_stride = 0); state k is inside iff
+ *                bit k is set.  Padded states are never drawn, so their bits do not matter.
+ *   own reported sites   W <= t < len, len = lens[data row] (device int64 [N] as phk_tracts; NULL = L for all; an entry outside
+ *                (W, L] is clamped and raises the bad-index flag).  Sites at or past len are still drawn -- the chain of draws
+ *                needs them -- and count for nothing.
+ *   a tract      a maximal run of consecutive own reported sites whose state is inside the set.  A tract that touches site W or
+ *                site len - 1 is counted at its VISIBLE length: what lies before W or past the row's end is not looked at.
+ *   stats        int32 [B, S, n_samples, 4 + C], C = n_edges + 1:
+ *                  0  own reported sites inside the set;
+ *                  1  number of tracts;
+ *                  2  length of the longest tract (0 if none);
+ *                  3  number of adjacent pairs (t - 1, t) of own reported sites, both >= W, whose states differ (the set plays
+ *                     no part);
+ *                  4 .. 3 + C  histogram of tract lengths: a tract of n sites falls in class #{e : edges[e] <= n}, so a length
+ *                     equal to an edge goes to the upper class;
+ *   edges        HOST array of n_edges strictly ascending int64 >= 1, 0 <= n_edges <= 15 (NULL allowed with n_edges = 0);
+ *   cover        int32 [B, S, nbin] or NULL, nbin = ceil((L - W) / bin), bins over the reported sites as in every other call:
+ *                the sum over the samples of the number of own reported sites of the bin that lie in a tract of min_len sites
+ *                or more (min_len >= 1).  cover / (n_samples x own sites of the bin) estimates P(the window lies in a tract
+ *                at least min_len long | o).  bin and min_len are ignored where cover is NULL;
+ *   ll           [B, S] double: bitwise what phk_posterior returns, as for phk_sample_paths.
+ * Everything is integer: sample r's row of stats depends on (seed, q, r) alone -- not on n_samples, the slabs or how the kernel
+ * groups samples, and on the plan only as far as the paths themselves do -- and cover, a sum of integers added in whatever order
+ * the units arrive, is the same for any slab size and any repeat of the call.  Per slab of the checkpoint store: the forward
+ * kernel of the plan a gradient call of this shape would run, as phk_sample_paths launches it, the reducing traceback, and where
+ * cover is wanted a kernel that adds the bins tracts cover whole (kept as an int32 difference row per sequence of the slab: that
+ * workspace is part of the slab arithmetic, phk_set_workspace_limit, and a large batch is cut into more slabs).  stats and cover
+ * are zeroed by the call.  The plan is read, never tuned or recorded: the call leaves phk_get_plan and the bits of every later
+ * call unchanged.  Stream-ordered; no two calls on one handle may overlap.  The underflow flag is raised as by phk_sample_paths.
+ * PHK_EINVAL, before anything is enqueued, for a NULL handle, NULL params / inds / ll / stats / masks, W outside [0, L),
+ * n_samples outside [1, 65535], mask_stride other than 0 or 1, n_edges outside [0, 15], edges not strictly ascending or
+ * edges[0] < 1, L - W >= 2^31 - 1, a non-NULL cover with bin < 1, min_len < 1 or n_samples x min(bin, L - W) >= 2^31, and
+ * phk_viterbi's prefold rules. */
+int phk_sample_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                      const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed,
+                      const uint64_t* masks, int64_t mask_stride, const int64_t* lens, const int64_t* edges, int n_edges, int bin,
+                      int64_t min_len, double* ll, int32_t* stats, int32_t* cover, void* stream);
+
 /* Posterior predictive simulation (the reference has no counterpart): n_rep replicate observation rows of L sites drawn from
  * the HMM of every (particle b, row s), laid under row s's accessibility mask; stored, or reduced on the fly to het counts
  * per bin and a histogram of hom-run lengths, or both.  Device-level like phk_param_map: no handle, no plan, no upload.

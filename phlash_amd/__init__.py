@@ -30,7 +30,8 @@ def __getattr__(name):
         from .decode import posterior_tmrca
         return posterior_tmrca
     if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check", "tract_posterior", "local_scan",
-                "LocalScan", "transition_counts", "TransitionCounts", "tmrca_band", "TmrcaBand"):
+                "LocalScan", "transition_counts", "TransitionCounts", "tmrca_band", "TmrcaBand", "path_tracts", "PathTracts", "tract_lengths",
+                "TractLengths", "TractSummary"):
         from . import decode
         return getattr(decode, name)
     if name in ("simulate_rows", "replicate_check", "Simulated", "ReplicateCheck"):

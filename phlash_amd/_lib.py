@@ -38,6 +38,8 @@ SIGNATURES = {
     "phk_pair_counts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "phk_viterbi": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "phk_sample_paths": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _vp, _vp, _i64, _vp]),
+    "phk_sample_tracts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _vp, _i64, _vp,
+                               ctypes.POINTER(ctypes.c_int64), _i, _i, _i64, _vp, _vp, _vp, _vp]),
     "phk_simulate": (_i, [_i, _i, _vp, _i64, _i64, _i64, _i64, _i64, _i64, ctypes.c_uint64, _i64, _vp, _i64, _vp, _vp, _i64, _i, _vp, _vp, _vp, _vp]),
     "phk_param_map": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_double, _vp, _i64, _vp, _vp, _vp]),
     "phk_param_map_rounded": (_i, [_i, _i, _i, ctypes.POINTER(ctypes.c_int32), ctypes.c_double, _vp, _i64, _vp, _vp, _vp, _vp]),

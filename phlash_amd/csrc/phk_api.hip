@@ -30,6 +30,7 @@ namespace phk {
     hipError_t launch_decode_##tag(int T, int nrm, const KArgs& a, const DArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_viterbi_##tag(int nrm, const KArgs& a, const VArgs& d, int nt, hipStream_t st);                   \
     hipError_t launch_sample_##tag(int T, int nrm, const KArgs& a, const SArgs& d, int nt, hipStream_t st);                \
+    hipError_t launch_sample_tracts_##tag(int T, int nrm, const KArgs& a, const XArgs& d, int nt, hipStream_t st);         \
     hipError_t launch_trans_##tag(int T, int nrm, const KArgs& a, const TArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_loo_##tag(int T, int nrm, const KArgs& a, const LArgs& d, int units, int nt, hipStream_t st);     \
     hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st); \
@@ -149,7 +150,7 @@ struct phk_handle {
     int K = 0, device = 0, dbl = 0;
     int64_t N = 0, L = 0, Lw = 0;
     uint32_t* packed = nullptr;
-    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops, pairs;
+    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops, pairs, tdiff;
     int64_t ws_limit = 0;
     int force_R = 0, force_T = 0, nrm = DEFAULT_NRM;
     int mode = -1;     // -1 auto, 0 serial, 1 segmented
@@ -1092,7 +1093,7 @@ int phk_destroy(phk_handle* h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_fwd) (void)hipEventDestroy(h->ev_fwd);
     if (h->side) (void)hipStreamDestroy(h->side);
-    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops, &h->pairs})
+    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops, &h->pairs, &h->tdiff})
         b->release();
     if (h->packed) (void)hipFree(h->packed);
     delete h;
@@ -1218,9 +1219,9 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
                                             "loo_kernel (serial sweep)", "loo_kernel (segment sweep)", "tract_kernel (serial sweep)",
                                             "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)",
                                             "pairs_kernel (serial sweep)", "pairs_kernel (segment sweep)", "moments_kernel (serial sweep)",
-                                            "moments_kernel (segment sweep)"};
+                                            "moments_kernel (segment sweep)", "sample_tracts_kernel"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 21 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 22 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
     if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
     return PHK_OK;
@@ -1954,6 +1955,140 @@ int phk_sample_paths(phk_handle* h, const void* params, int64_t pstride_b, int64
             if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
             e = smp(plan.T, h->nrm, a, d, 256, st);
             if (e != hipSuccess) return fail(PHK_EHIP, "sampling kernel launch (K=%d T=%d): %s", K, plan.T, hipGetErrorString(e));
+        }
+    }
+    return PHK_OK;
+}
+
+}  // extern "C"
+
+namespace phk {
+
+// cover += bin x the prefix sum of the difference row (launch_sample_tracts.hip: tract_emit).  One wave per sequence of the
+// launch: every lane sums a run of ceil(nbin / 64) bins, the runs are scanned across the wave, and a second pass adds.  Both loops
+// are bounded by that run length, a kernel argument.
+__global__ __launch_bounds__(64) void cover_finalize_kernel(int32_t* cover, const int32_t* diff, int64_t B, int64_t b0, int64_t s0,
+                                                            int64_t S_call, int nbin, int bin, int per_lane) {
+    const int64_t seq = blockIdx.x;
+    const int64_t ss = seq / B, bb = seq - ss * B;  // chunk-major order, as the traceback numbers its sequences
+    const int64_t q = (b0 + bb) * S_call + s0 + ss;
+    const int32_t* d = diff + seq * nbin;
+    int32_t* c = cover + q * nbin;
+    const int lane = threadIdx.x;
+    const int lo = lane * per_lane < nbin ? lane * per_lane : nbin;
+    const int hi = lo + per_lane < nbin ? lo + per_lane : nbin;
+    int sum = 0;
+    for (int g = lo; g < hi; ++g) sum += d[g];
+    int incl = sum;
+#pragma unroll
+    for (int k = 1; k < 64; k <<= 1) {
+        const int up = __shfl_up(incl, k, 64);
+        if (lane >= k) incl += up;
+    }
+    int run = incl - sum;
+    for (int g = lo; g < hi; ++g) {
+        run += d[g];
+        if (run != 0) c[g] += bin * run;
+    }
+}
+
+}  // namespace phk
+
+extern "C" {
+
+// Sampled tract spectra (phk_sample_tracts): phk_sample_paths' body with the reducing traceback in the path-storing one's place
+// -- the same plan read, the same forward leg, the same slabs.  The difference rows of cover (an int32 per bin and sequence of a
+// slab) are workspace of the call and part of the slab arithmetic.
+int phk_sample_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold, const int64_t* inds,
+                      int64_t B, int64_t S, int64_t W, int64_t n_samples, uint64_t seed, const uint64_t* masks, int64_t mask_stride,
+                      const int64_t* lens, const int64_t* edges, int n_edges, int bin, int64_t min_len, double* ll, int32_t* stats,
+                      int32_t* cover, void* stream) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    if (!params || !inds || !ll || !stats || !masks) return fail(PHK_EINVAL, "params, inds, ll, stats and masks must be non-NULL device pointers");
+    if (W < 0 || W >= h->L) return fail(PHK_EINVAL, "W=%lld outside [0, L=%lld)", (long long)W, (long long)h->L);
+    if (n_samples < 1 || n_samples > 65535) return fail(PHK_EINVAL, "n_samples=%lld outside [1, 65535]", (long long)n_samples);
+    if (mask_stride != 0 && mask_stride != 1) return fail(PHK_EINVAL, "mask_stride=%lld must be 0 (one set) or 1 (one per particle)", (long long)mask_stride);
+    if (n_edges < 0 || n_edges > phk::TRACT_MAX_EDGES) return fail(PHK_EINVAL, "n_edges=%d outside [0, %d]", n_edges, phk::TRACT_MAX_EDGES);
+    if (n_edges > 0 && !edges) return fail(PHK_EINVAL, "edges is NULL with n_edges=%d", n_edges);
+    for (int e = 0; e < n_edges; ++e) {
+        if (edges[e] < 1) return fail(PHK_EINVAL, "edges[%d]=%lld must be >= 1", e, (long long)edges[e]);
+        if (e > 0 && edges[e] <= edges[e - 1]) return fail(PHK_EINVAL, "edges must be strictly ascending (edges[%d]=%lld after %lld)", e, (long long)edges[e], (long long)edges[e - 1]);
+    }
+    if (h->L - W >= INT32_MAX) return fail(PHK_EINVAL, "L - W=%lld does not fit the int32 statistics", (long long)(h->L - W));
+    if (cover) {
+        if (bin < 1) return fail(PHK_EINVAL, "bin=%d must be >= 1", bin);
+        if (min_len < 1) return fail(PHK_EINVAL, "min_len=%lld must be >= 1", (long long)min_len);
+        if (n_samples * std::min<int64_t>(bin, h->L - W) >= ((int64_t)1 << 31))
+            return fail(PHK_EINVAL, "n_samples=%lld x min(bin=%d, L - W=%lld) does not fit the int32 cover", (long long)n_samples, bin, (long long)(h->L - W));
+    }
+    if (B < 0 || S < 0) return fail(PHK_EINVAL, "B and S must be >= 0");
+    if (int rc = check_prefold(h, prefold, pstride_b, pstride_s); rc != PHK_OK) return rc;
+    if (B == 0 || S == 0) return PHK_OK;
+    Launchers l;
+    if (!pick_launchers(h, &l)) return fail(PHK_EUNSUPPORTED, "K=%d not compiled in", h->K);
+    const auto smp = PHK_PICK(sample_tracts, h);
+    HIP_TRY(hipSetDevice(h->device));
+    hipStream_t st = (hipStream_t)stream;
+    h->last_stream = st;  // (phk_underflow_risk reads the flag word behind it)
+    const int K = h->K;
+    const CallShape c = {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream};
+    const int64_t nbin = cover ? (h->L - W + bin - 1) / bin : 0;
+    const int ncol = 4 + n_edges + 1;
+
+    int64_t Bs, Ss;
+    if (int rc = slab_for(h, B, S, nbin * (int64_t)sizeof(int32_t), &Bs, &Ss); rc != PHK_OK) return rc;
+    Plan plan;
+    int Rf;
+    if (int rc = read_plan(h, Bs, Ss, W, &plan, &Rf); rc != PHK_OK) return rc;
+    const bool dense = dense_capable(h) && Rf == 16;
+    if (dense) {
+        if (int rc = size_dense_ops(h, c, Bs, Ss); rc != PHK_OK) return rc;
+    }
+    if (cover) {
+        if (int rc = h->tdiff.ensure((size_t)(Bs * Ss * nbin) * sizeof(int32_t)); rc != PHK_OK) return rc;
+        HIP_TRY(hipMemsetAsync(cover, 0, (size_t)(B * S * nbin) * sizeof(int32_t), st));
+    }
+    HIP_TRY(hipMemsetAsync(stats, 0, (size_t)(B * S * n_samples * ncol) * sizeof(int32_t), st));
+
+    for (int64_t b0 = 0; b0 < B; b0 += Bs) {
+        const int64_t nb = std::min(Bs, B - b0);
+        for (int64_t s0 = 0; s0 < S; s0 += Ss) {
+            const int64_t ns = std::min(Ss, S - s0);
+            phk::KArgs a = base_kargs(h, c, b0, nb, s0, ns);
+            a.seg_blocks = seg_blocks(plan.T);
+            set_budgets(h, &a, plan.T, (h->L + plan.T - 1) / plan.T + 8);  // (the traceback makes one iteration per block)
+            if (dense) {
+                if (int rc = slab_dense_ops(h, &a, s0, st); rc != PHK_OK) return rc;
+            }
+            phk::XArgs d;
+            d.stats = stats;
+            d.cover = cover;
+            d.diff = cover ? (int32_t*)h->tdiff.p : nullptr;
+            d.masks = masks + b0 * mask_stride;
+            d.mask_stride = mask_stride;
+            d.lens = lens;
+            d.n_samples = n_samples;
+            d.seed = seed;
+            d.b0 = b0;
+            d.s0 = s0;
+            d.S_call = S;
+            d.bin = cover ? bin : 1;
+            d.nbin = (int32_t)nbin;
+            d.min_len = (int32_t)std::min<int64_t>(min_len, INT32_MAX);
+            d.ncol = ncol;
+            for (int e = 0; e < phk::TRACT_MAX_EDGES; ++e) d.edges[e] = e < n_edges ? (int32_t)std::min<int64_t>(edges[e], INT32_MAX) : INT32_MAX;
+            if (cover) HIP_TRY(hipMemsetAsync(h->tdiff.p, 0, (size_t)(nb * ns * nbin) * sizeof(int32_t), st));
+            // (the forward kernel of a segmented plan runs with the workgroup it has beside the beta scan, as in run_sweep)
+            hipError_t e = l.fwd(Rf, plan.T, h->nrm, true, a, plan.segmented ? 256 : FWD_NT, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "forward kernel launch (K=%d R=%d T=%d): %s", K, Rf, plan.T, hipGetErrorString(e));
+            e = smp(plan.T, h->nrm, a, d, 256, st);
+            if (e != hipSuccess) return fail(PHK_EHIP, "tract-sampling kernel launch (K=%d T=%d): %s", K, plan.T, hipGetErrorString(e));
+            if (cover) {
+                hipLaunchKernelGGL(phk::cover_finalize_kernel, dim3((unsigned)(nb * ns)), dim3(64), 0, st, cover, (const int32_t*)h->tdiff.p, nb, b0, s0, S,
+                                   (int)nbin, bin, (int)((nbin + 63) / 64));
+                e = hipGetLastError();
+                if (e != hipSuccess) return fail(PHK_EHIP, "cover finalize kernel launch: %s", hipGetErrorString(e));
+            }
         }
     }
     return PHK_OK;

@@ -32,6 +32,27 @@ struct SArgs {
     int64_t S_call;       // ... the call's S: q = (b0 + b) * S_call + (s0 + s) numbers the sequences of the call
 };
 
+// sampled tract spectra (launch_sample_tracts.hip): the traceback of SArgs with the paths reduced in place of stored
+constexpr int TRACT_MAX_EDGES = 15;
+struct XArgs {
+    int32_t* stats;         // [B, S, n_samples, 4 + C] of the CALL, zeroed before the first launch (C = n_edges + 1)
+    int32_t* cover;         // [B, S, nbin] of the CALL, zeroed before the first launch, or null
+    int32_t* diff;          // workspace [B S of the launch, nbin], zeroed before the launch: +1 / -1 at the first / behind the last
+                            // bin a qualifying tract covers whole (null exactly when cover is)
+    const uint64_t* masks;  // [B] (mask_stride = 1) or [1] (0) of the launch: bit k set = state k is inside the set
+    int64_t mask_stride;
+    const int64_t* lens;    // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    int64_t n_samples;      // samples per sequence (>= 1)
+    uint64_t seed;          // Philox key
+    int64_t b0, s0;         // position of the slab in the call, and ...
+    int64_t S_call;         // ... the call's S: q = (b0 + b) * S_call + (s0 + s) numbers the sequences of the call
+    int32_t bin;            // reported sites per bin of cover (>= 1)
+    int32_t nbin;           // bins per sequence: ceil((Ltot - W) / bin)
+    int32_t min_len;        // cover counts the sites of tracts at least this long (>= 1)
+    int32_t ncol;           // 4 + C
+    int32_t edges[TRACT_MAX_EDGES];  // class of a tract of n sites = #{e : edges[e] <= n}; unused entries INT32_MAX
+};
+
 // transition posteriors (launch_trans.hip)
 struct TArgs {
     int64_t bin;          // scored sites per bin (>= 1)

@@ -9,8 +9,10 @@ the leave-one-out check of the observations from its predictive sweep (``PSMCKer
 tract probabilities from its tract sweep (``PSMCKernel.tracts`` -> ``phk_tracts``) and the local likelihood-ratio scans from its
 local-ratio sweep (``PSMCKernel.local_ratio`` -> ``phk_local_ratio``) and the expected transition matrix from its pair-count sweep
 (``PSMCKernel.pair_counts`` -> ``phk_pair_counts``) and the error band of the TMRCA track from its bin-moment sweep
-(``PSMCKernel.bin_moments`` -> ``phk_bin_moments``); this module only builds the models, pads ragged inputs,
-averages, counts and run-length encodes.  There is no CPU path.
+(``PSMCKernel.bin_moments`` -> ``phk_bin_moments``) and the tract-length spectra from its reducing sampling traceback
+(``PSMCKernel.sample_tracts`` -> ``phk_sample_tracts``); this module only builds the models, pads ragged inputs,
+averages, counts and run-length encodes.  There is no CPU path to the kernels' results; ``path_tracts`` is plain torch on paths
+a caller already holds.
 """
 
 from __future__ import annotations
@@ -561,3 +563,166 @@ def tmrca_segments(path, values=None):
         return row, start, end, state
     v = torch.as_tensor(values, dtype=torch.float64, device=p.device)
     return row, start, end, state, v[state]
+
+
+class PathTracts(NamedTuple):
+    """What ``path_tracts`` returns: int32 tensors on the device of the paths."""
+
+    counts: torch.Tensor  # [..., n_samples, 4]: sites inside the set, tracts, longest tract, changes of state
+    hist: torch.Tensor  # [..., n_samples, C]: tracts per length class, C = len(edges) + 1
+    cover: torch.Tensor | None  # [..., nbin]: sites in tracts of at least min_len sites, summed over the samples, or None
+
+
+def path_tracts(paths, in_set, *, edges=(), lens=None, min_len: int = 1, bin: int | None = None) -> PathTracts:
+    """The tracts of stored state paths: what ``PSMCKernel.sample_tracts`` computes inside the kernel without storing a path, here
+    from paths a caller holds (``PSMCKernel.sample_paths``, ``sample_tmrca``), in vectorised torch on the device of ``paths``.
+
+    paths: integer tensor [..., n_samples, n] of states, the sites in order (a state of 255, past a Viterbi row's end, is
+        outside every set).
+    in_set: bool [M], or [B, M] with one row per entry of the FIRST dimension of ``paths``: the states that are inside.
+    lens: integers broadcastable to ``paths.shape[:-2]``: how many of the n sites are the row's own (for paths of a kernel with
+        ``overlap``: its ``lens`` minus the overlap); sites behind count for nothing.  None: all n.
+    A tract is a maximal run of consecutive own sites whose state is inside; one that touches the first or the last own site
+    is counted at its visible length.  ``counts`` [..., n_samples, 4]: own sites inside the set, number of tracts, length of the
+    longest tract (0 if none), number of adjacent pairs of own sites whose states differ (whatever the set).  ``hist``
+    [..., n_samples, C]: ``edges`` (strictly ascending lengths >= 1) cut the tract lengths into C = len(edges) + 1 classes, a
+    tract of m sites falling in class #{e : edges[e] <= m}.  With ``bin`` given, ``cover`` [..., nbin], nbin = ceil(n / bin):
+    per bin of ``bin`` sites the number of own sites that lie in a tract of at least ``min_len`` sites, summed over the
+    samples.  Returns ``PathTracts(counts, hist, cover)``, int32."""
+    p = torch.as_tensor(paths)
+    assert p.ndim >= 2 and not p.dtype.is_floating_point, "paths: integer [..., n_samples, n]"
+    dev = p.device
+    edges = [int(e) for e in edges]
+    assert all(e >= 1 for e in edges) and all(a < b for a, b in zip(edges, edges[1:])), "edges: strictly ascending lengths >= 1"
+    assert int(min_len) >= 1 and (bin is None or int(bin) >= 1)
+    lead, ns, n = p.shape[:-2], p.shape[-2], p.shape[-1]
+    C = len(edges) + 1
+    m = torch.as_tensor(in_set, device=dev).to(torch.bool)
+    assert m.ndim in (1, 2) and m.shape[-1] <= 256, "in_set: bool [M] or [B, M]"
+    table = torch.zeros(m.shape[:-1] + (256,), dtype=torch.bool, device=dev)  # (255 and every state beyond M: outside)
+    table[..., : m.shape[-1]] = m
+    z = p.long()
+    if m.ndim == 1:
+        inside = table[z]
+    else:
+        assert p.ndim >= 3 and m.shape[0] == p.shape[0], "in_set [B, M]: one row per entry of the first dimension of paths"
+        inside = torch.gather(table.reshape((m.shape[0],) + (1,) * (p.ndim - 2) + (256,)).expand(p.shape[:-1] + (256,)), -1, z)
+    own_len = torch.full(lead, n, dtype=torch.int64, device=dev) if lens is None else \
+        torch.as_tensor(lens, device=dev).to(torch.int64).expand(lead).clamp(0, n)
+    R = int(np.prod(lead, dtype=np.int64)) * ns
+    own = torch.arange(n, device=dev)[None, :] < own_len.reshape(-1, 1).repeat_interleave(ns, 0)  # [R, n]
+    z = z.reshape(R, n)
+    inside = inside.reshape(R, n) & own
+    pad = torch.zeros((R, 1), dtype=torch.bool, device=dev)
+    first = inside & ~torch.cat([pad, inside[:, :-1]], 1)  # the first site of a tract
+    last = inside & ~torch.cat([inside[:, 1:], pad], 1)  # its last site
+    row, start = first.nonzero(as_tuple=True)  # (row-major order: the k-th start and the k-th end are one tract's)
+    _, end = last.nonzero(as_tuple=True)
+    length = end - start + 1
+    counts = torch.zeros((R, 4), dtype=torch.int64, device=dev)
+    counts[:, 0] = inside.sum(1)
+    counts[:, 1] = first.sum(1)
+    counts[:, 2] = torch.zeros(R, dtype=torch.int64, device=dev).scatter_reduce(0, row, length, "amax", include_self=True)
+    counts[:, 3] = ((z[:, 1:] != z[:, :-1]) & own[:, 1:]).sum(1)
+    cls = torch.bucketize(length, torch.tensor(edges, dtype=torch.int64, device=dev), right=True)  # = #{e : edges[e] <= length}
+    hist = torch.zeros(R * C, dtype=torch.int64, device=dev).index_add_(0, row * C + cls, torch.ones_like(cls)).reshape(R, C)
+    cover = None
+    if bin is not None:
+        bin = int(bin)
+        nbin = (n + bin - 1) // bin
+        keep = length >= int(min_len)
+        d = torch.zeros(R * (n + 1), dtype=torch.int32, device=dev)  # +1 where a long tract starts, -1 behind its end
+        one = torch.ones(int(keep.sum()), dtype=torch.int32, device=dev)
+        d.index_add_(0, row[keep] * (n + 1) + start[keep], one)
+        d.index_add_(0, row[keep] * (n + 1) + end[keep] + 1, -one)
+        covered = torch.cumsum(d.reshape(R, n + 1)[:, :n], 1).reshape(-1, ns, n).sum(1)  # [rows, n]: samples whose long tract holds the site
+        covered = torch.cat([covered, covered.new_zeros((covered.shape[0], nbin * bin - n))], 1)
+        cover = covered.reshape(-1, nbin, bin).sum(2).to(torch.int32).reshape(lead + (nbin,))
+    return PathTracts(counts.to(torch.int32).reshape(lead + (ns, 4)), hist.to(torch.int32).reshape(lead + (ns, C)), cover)
+
+
+class TractSummary(NamedTuple):
+    """Mean and central 95 % interval of a per-(model, sample) count, over models x samples with equal weight (float64)."""
+
+    mean: torch.Tensor
+    lo: torch.Tensor  # the 2.5 % quantile
+    hi: torch.Tensor  # the 97.5 % quantile
+
+
+class TractLengths(NamedTuple):
+    """What ``tract_lengths`` returns: device tensors per row ([N, ...]) for a matrix; for a list of contigs ``in_long`` is a list
+    with one tensor per contig, cut to the contig's own bins."""
+
+    spectrum: TractSummary  # [N, C]: tracts per length class
+    n_tracts: TractSummary  # [N]: number of tracts
+    longest: TractSummary  # [N]: length of the longest tract, in windows
+    inside: TractSummary  # [N]: windows inside the set
+    in_long: object  # [N, nbin] float64: estimated P(the window lies in a tract of at least min_len windows | data)
+    counts: torch.Tensor  # [B, N, n_samples, 4] int32: the raw counts per model and sample (``PSMCKernel.sample_tracts``)
+    hist: torch.Tensor  # [B, N, n_samples, C] int32: the raw histograms
+
+
+def _summary(x: torch.Tensor) -> TractSummary:
+    """x [B, N, n_samples, ...] -> per row over models x samples"""
+    x = x.to(torch.float64).transpose(0, 1)  # [N, B, n_samples, ...]
+    x = x.reshape((x.shape[0], x.shape[1] * x.shape[2]) + tuple(x.shape[3:]))
+    q = torch.quantile(x, torch.tensor([0.025, 0.975], dtype=torch.float64, device=x.device), dim=1)
+    return TractSummary(x.mean(1), q[0], q[1])
+
+
+def tract_lengths(dms, data, t_max, t_min: float = 0.0, *, n_samples: int = 64, seed: int = 0, edges=(10, 100, 1000), min_len: int = 100,
+                  bin: int = 100, window_size: int = 100, in_set=None, device=None, double_precision: bool = False) -> TractLengths:
+    """How many tracts every row of ``data`` has, how long they are, and which windows lie in a long one: the tracts of TMRCA in
+    [t_min, t_max) (``t_max`` small: runs of homozygosity, IBD segments) in ``n_samples`` posterior paths per model, reduced on
+    the GPU without a path being stored (``PSMCKernel.sample_tracts``).  None of this is additive over sites, so no exact sweep
+    gives it; ``tract_posterior`` answers the other question, whether a fixed bin lies inside the range entirely.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``; the set of
+        states of each model comes from [t_min, t_max) by ``tract_posterior``'s rule (a state is inside when its whole interval
+        is).  ``in_set`` (bool [M] or [len(dms), M]) overrides it.
+    data: int8 [N, L] het matrix of whole-contig rows, or a list of ``RawContig`` (or of int8 matrices) of different lengths:
+        they are padded with missing windows and each row's own length goes to the kernel, which counts nothing behind it.
+    edges: tract lengths in windows that cut the spectrum into len(edges) + 1 classes (a length equal to an edge goes up).
+    min_len, bin: ``in_long`` is, per bin of ``bin`` windows, the share of (model, sample, own window of the bin) whose window
+        lies in a tract of at least ``min_len`` windows.
+    Returns ``TractLengths``; the summaries weigh models x samples equally.  The same ``seed`` gives the same numbers."""
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if in_set is None:
+        assert float(t_min) < float(t_max), "the TMRCA range [t_min, t_max) is empty"
+        w = np.empty((len(dms), M), dtype=bool)
+        for i, dm in enumerate(dms):
+            t = np.asarray(torch.as_tensor(dm.eta.t, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(M)
+            lo, hi = t, np.append(t[1:], np.inf)
+            w[i] = (lo >= float(t_min)) & (hi <= float(t_max))
+    else:
+        w = np.asarray(in_set.cpu() if isinstance(in_set, torch.Tensor) else in_set).astype(bool)
+        assert w.shape in ((M,), (len(dms), M)), f"in_set: [{M}] or [{len(dms)}, {M}]"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    if spans is not None:
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    dev = kern.device
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.sample_tracts(pp, torch.arange(rows.shape[0], device=dev), in_set=w, n_samples=n_samples, seed=seed, edges=edges,
+                             lens=lens, min_len=min_len, bin=bin)
+    own = torch.as_tensor(lens if lens is not None else np.full(rows.shape[0], rows.shape[1]), dtype=torch.int64, device=dev)
+    sites = (own[:, None] - torch.arange(out.cover.shape[-1], dtype=torch.int64, device=dev)[None, :] * int(bin)).clamp_(0, int(bin))
+    total = out.cover.sum(0, dtype=torch.int64).to(torch.float64)  # [N, nbin] over the models
+    in_long = total / (len(dms) * int(n_samples) * sites.clamp(min=1)).to(torch.float64)
+    if spans is not None:
+        in_long = [in_long[r : r + n, : (length + int(bin) - 1) // int(bin)] for r, n, length in spans]
+    c = out.counts
+    return TractLengths(_summary(out.hist), _summary(c[..., 1]), _summary(c[..., 2]), _summary(c[..., 0]), in_long, c, out.hist)

@@ -507,3 +507,38 @@ class HipEngine:
         )
         _lib.check(rc)
         return ll, paths
+
+    def sample_tracts(self, params: torch.Tensor, inds: torch.Tensor, masks: torch.Tensor, warmup: int = 0, n_samples: int = 1,
+                      seed: int = 0, edges=(), lens: torch.Tensor | None = None, min_len: int = 1, bin: int | None = None):
+        """Sampled tract spectra (``phk_sample_tracts``): params / inds / n_samples / seed as ``sample_paths``, whose paths this
+        call draws and reduces without storing them.  ``masks``: int64 [B] or [1] on the device, the state set of every particle
+        (or of all) as a bit pattern, bit k set = state k is inside (bit 63 is the sign bit of the int64).  ``edges``: up to 15
+        strictly ascending tract lengths >= 1 that cut the length histogram into C = len(edges) + 1 classes (a length equal to an
+        edge goes to the upper class).  ``lens`` as ``transitions``.  Returns (ll [B, S] float64, stats [B, S, n_samples, 4 + C]
+        int32, cover [B, S, nbin] int32 or None): per sample the own reported sites inside the set, the number of tracts, the
+        longest tract, the changes of state and the histogram; with ``bin`` given, per bin of ``bin`` reported sites the number
+        of own sites, summed over the samples, that lie in a tract of at least ``min_len`` sites."""
+        assert 0 <= int(warmup) < self.L and 1 <= int(n_samples) <= 65535 and 0 <= int(seed) < 1 << 64
+        edges = [int(e) for e in edges]
+        assert len(edges) <= 15 and all(e >= 1 for e in edges) and all(a < b for a, b in zip(edges, edges[1:])), \
+            f"edges: at most 15 strictly ascending lengths >= 1, got {edges}"
+        assert masks.is_cuda and masks.device == self.device and masks.dtype == torch.int64, "masks: int64 on the device"
+        assert masks.shape in ((1,), (params.shape[0],)), f"masks: [1] or [B], got {tuple(masks.shape)}"
+        c = self._sweep_call(params, inds, lens)
+        masks = masks.contiguous()
+        C = len(edges) + 1
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        stats = torch.empty((c.B, c.S, int(n_samples), 4 + C), dtype=torch.int32, device=self.device)
+        cover = None
+        if bin is not None:
+            assert int(bin) >= 1 and int(min_len) >= 1
+            assert int(n_samples) * min(int(bin), self.L - int(warmup)) < 1 << 31, "n_samples x bin does not fit the int32 cover"
+            cover = torch.empty((c.B, c.S, self._nbin(warmup, bin)), dtype=torch.int32, device=self.device)
+        earr = (ctypes.c_int64 * max(len(edges), 1))(*edges)
+        rc = _lib.load().phk_sample_tracts(
+            *c.head, *c.grid, int(warmup), int(n_samples), int(seed), masks.data_ptr(), 1 if masks.shape[0] == c.B and c.B > 1 else 0,
+            c.lens, earr, len(edges), int(bin) if bin is not None else 1, int(min_len), ll.data_ptr(), stats.data_ptr(),
+            cover.data_ptr() if cover is not None else None, c.stream,
+        )
+        _lib.check(rc)
+        return ll, stats, cover

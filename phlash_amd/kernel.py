@@ -60,6 +60,15 @@ class PathSample(NamedTuple):
     paths: torch.Tensor  # [..., n_samples, L - overlap] uint8: the sampled states at the scored sites
 
 
+class TractSample(NamedTuple):
+    """What ``PSMCKernel.sample_tracts`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    counts: torch.Tensor  # [..., n_samples, 4] int32: sites inside the set, tracts, longest tract, changes of state
+    hist: torch.Tensor  # [..., n_samples, C] int32: tracts per length class, C = len(edges) + 1
+    cover: torch.Tensor | None  # [..., nbin] int32: sites in tracts of at least min_len sites, summed over the samples, or None
+
+
 class Transitions(NamedTuple):
     """What ``PSMCKernel.transitions`` returns (device tensors, batch dims stripped as ``loglik`` strips them)."""
 
@@ -488,6 +497,36 @@ class PSMCKernel:
             pa, inds, added_B, added_S = self._model_inputs(pp, index)
             ll, paths = _guarded(self, "sample_paths", pa, inds, warmup=self.overlap, n_samples=int(n_samples), seed=int(seed))
         return PathSample(self._strip(ll, added_B, added_S), self._strip(paths, added_B, added_S))
+
+    # ---- sampled tract spectra -------------------------------------------------------------------
+    def sample_tracts(self, pp, index, *, in_set, n_samples: int = 1, seed: int = 0, edges=(), lens=None, min_len: int = 1,
+                      bin: int | None = None) -> TractSample:
+        """What is not additive over sites, from sampled paths that are never stored: the paths ``sample_paths`` draws for the same
+        ``seed`` (draw for draw), reduced inside the kernel to their tracts -- maximal runs of consecutive scored sites whose
+        state lies in ``in_set`` (bool [M], or [B, M] with one row per particle of ``pp``).  Per sample ``counts``
+        [..., n_samples, 4] = (sites inside the set, number of tracts, longest tract, changes of state between adjacent scored
+        sites) and ``hist`` [..., n_samples, C], the tracts by length class: ``edges`` (up to 15 strictly ascending lengths >= 1)
+        cut the lengths into C = len(edges) + 1 classes, a length equal to an edge going to the upper one.  With ``bin`` given,
+        ``cover`` [..., nbin] (nbin = ceil((L - overlap) / bin)): per bin of ``bin`` scored sites, the number of the bin's own
+        sites that lie in a tract of at least ``min_len`` sites, summed over the samples -- divided by n_samples x the bin's own
+        sites, the estimated probability that a window lies in such a tract.  ``lens`` ([N] integers, one own length per row of
+        the kernel's data, ``overlap < len <= L``): sites at or past a row's own length are drawn and count for nothing.  A
+        tract that touches the first scored site or the row's last own site is counted at its visible length.  Chunk(s)
+        ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as ``loglik``).  ``phlash_amd.path_tracts`` computes
+        the same arrays from stored paths.  Returns ``TractSample(ll, counts, hist, cover)``, int32 device tensors (ll float64);
+        no gradient."""
+        with torch.no_grad():
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            m = np.asarray(in_set.cpu() if isinstance(in_set, torch.Tensor) else in_set).astype(bool)
+            assert m.shape in ((self.M,), (pa.shape[0], self.M)), f"in_set: [{self.M}] or [{pa.shape[0]}, {self.M}], got {m.shape}"
+            words = [sum(1 << k for k in range(self.M) if row[k]) for row in m.reshape(-1, self.M)]
+            masks = torch.tensor([w - (1 << 64) if w >= 1 << 63 else w for w in words], dtype=torch.int64, device=self.device)
+            lens = self._lens_tensor(lens)
+            ll, stats, cover = _guarded(self, "sample_tracts", pa, inds, masks, warmup=self.overlap, n_samples=int(n_samples),
+                                        seed=int(seed), edges=tuple(int(e) for e in edges), lens=lens, min_len=int(min_len),
+                                        bin=None if bin is None else int(bin))
+        strip = lambda x: None if x is None else self._strip(x, added_B, added_S)  # noqa: E731
+        return TractSample(strip(ll), strip(stats[..., :4]), strip(stats[..., 4:]), strip(cover))
 
     # ---- fused evaluation used by the sampler -------------------------------------------------
     def _inds_tensor(self, inds) -> torch.Tensor:
