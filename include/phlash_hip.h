@@ -314,6 +314,42 @@ int phk_local_ratio(phk_handle* h, const void* params, int64_t pstride_b, int64_
                     const int64_t* inds, int64_t B, int64_t S, int64_t W, int bin, const int64_t* lens,
                     double* ll, void* logratio, void* stream);
 
+/* Interval tracts (the reference has no counterpart): phk_tracts over intervals with arbitrary ends, each with a state set of its
+ * own, as a log -- how sure the data are of a called segment.  For each chunk position s of the call a list of intervals in
+ * REPORTED sites (position p is site W + p, as the path of phk_viterbi), disjoint, sorted and half-open, 0 <= start_j < end_j <=
+ * len - W; interval j has a state set S_j given as a 64-bit mask, bit k set = state k is inside (bits at or above K are not
+ * read).  Conventions of phk_tracts: z_0 ~ pi precedes site 0, alpha_{-1} = pi, beta_t holds the emissions of sites t+1 .. L-1
+ * only, a missing site has e = 1 and is restricted to the set all the same.  With s = W + start_j, e = W + end_j - 1:
+ *   q_e     = beta_e
+ *   q_{t-1} = A (1_{S_j} .* e_{o_t} .* q_t)      for t = e, e-1, .., s
+ *   logp_j  = log sum_i alpha_{s-1}(i) q_{s-1}(i)  -  log sum_i alpha_{s-1}(i) beta_{s-1}(i)
+ *           = log P(z_s .. z_e in S_j | o)   for sequence (b, s).
+ *   iv_off     device int64 [S + 1]: the intervals of chunk position s are iv_off[s] .. iv_off[s + 1] - 1 (CSR; iv_off[0] = 0,
+ *              n_iv = iv_off[S]); the lists are shared by the particles;
+ *   iv_start, iv_end   device int64 [n_iv];
+ *   masks      device uint64 [B, n_iv] with row stride mstride_b, or [n_iv] with mstride_b = 0 (one set per interval for all
+ *              particles);
+ *   max_len    an upper bound on end - start over the call (>= 1): it sizes the loop budget of a unit of the segmented plan;
+ *   logp       device double [B, n_iv] for both handle types, natural log; one writer per entry;
+ *   ll         [B, S] double, required: bitwise what phk_posterior returns on the same plan;
+ *   lens       device int64 [N] or NULL: the own length of every data row, the bound of its intervals.
+ * q carries a power-of-two exponent of its own relative to beta, as in phk_local_ratio: a tract of thousands of sites whose
+ * probability is far below the float range is right as a log.  A mask with all K bits set gives exactly 0, an empty mask -inf;
+ * an interval's bits do not depend on the other intervals of the call, on slabs or on the order of the units.  One small kernel
+ * checks every list before the first sweep: a list that is not sorted and disjoint, holds an empty interval, one outside
+ * [0, len - W] or one longer than max_len raises the bad-index flag (phk_underflow_risk) and all its logp are NaN; the other
+ * lists are not affected.  An interval whose denominator is not positive is written as 0 and raises the underflow flag.  n_iv = 0
+ * computes ll only (masks and logp must still point at one element).  An interval belongs to the unit of the segmented plan
+ * that holds its last site; the unit walks left to the interval's first site.  params / prefold / inds / strides as
+ * phk_loglik_prefolded; plan legs, slabs and stream ordering are phk_posterior's (a hybrid plan runs as its serial half); the
+ * plan is read, never tuned or recorded.  Stream-ordered; no two calls on one handle may overlap.  PHK_EINVAL, before anything is
+ * enqueued, for a NULL handle, NULL iv_off / iv_start / iv_end / masks / logp, max_len < 1, mstride_b < 0, NULL params / inds /
+ * ll, W outside [0, L]. */
+int phk_interval_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                        const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t max_len, const int64_t* lens,
+                        const int64_t* iv_off, const int64_t* iv_start, const int64_t* iv_end, const uint64_t* masks,
+                        int64_t mstride_b, double* ll, double* logp, void* stream);
+
 /* Pair counts (the reference has no counterpart): the full pair posterior summed along the row,
  *   counts[b, s, i, j] = sum over the row's own scored sites t of xi_t(i, j),    xi_t(i, j) = P(z_prev = i, z_t = j | o),
  * the expected number of moves from TMRCA state i (the ORIGIN, first index) to state j: the Baum-Welch transition statistic, the

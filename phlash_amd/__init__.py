@@ -31,7 +31,7 @@ def __getattr__(name):
         return posterior_tmrca
     if name in ("viterbi_tmrca", "tmrca_segments", "sample_tmrca", "posterior_changes", "predictive_check", "tract_posterior", "local_scan",
                 "LocalScan", "transition_counts", "TransitionCounts", "tmrca_band", "TmrcaBand", "path_tracts", "PathTracts", "tract_lengths",
-                "TractLengths", "TractSummary"):
+                "TractLengths", "TractSummary", "segment_support", "SegmentSupport"):
         from . import decode
         return getattr(decode, name)
     if name in ("simulate_rows", "replicate_check", "Simulated", "ReplicateCheck"):

@@ -35,6 +35,7 @@ SIGNATURES = {
     "phk_tracts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp]),
     "phk_bin_moments": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _i64, _vp, _vp, _vp, _vp, _vp]),
     "phk_local_ratio": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i, _vp, _vp, _vp, _vp]),
+    "phk_interval_tracts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _vp, _vp]),
     "phk_pair_counts": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp]),
     "phk_viterbi": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _i64, _vp]),
     "phk_sample_paths": (_i, [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _i64, ctypes.c_uint64, _vp, _vp, _i64, _vp]),

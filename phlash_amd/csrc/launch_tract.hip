@@ -22,18 +22,7 @@ namespace phk {
 constexpr int OVERRUN_TRACT_SERIAL = 14;
 constexpr int OVERRUN_TRACT_SEG = 15;
 
-// q <- A (em .* q): Lane::bt_site's recursion without a rescale of its own (q takes beta's)
-template <typename L>
-__device__ __forceinline__ void tract_step(const L& lane, typename L::V (&q)[L::NP], const typename L::V (&em)[L::NP]) {
-    using V = typename L::V;
-    constexpr int NP = L::NP;
-    V w[NP], svw[NP], pbw[NP], cb;
-#pragma unroll
-    for (int h = 0; h < NP; ++h) w[h] = q[h] * em[h];
-    lane.scans_adj(w, svw, pbw, cb);
-#pragma unroll
-    for (int h = 0; h < NP; ++h) q[h] = lane.beta_prev(h, w, svw, pbw, cb);
-}
+// (q <- A (em .* q) is tract_step of sweep_common.h: Lane::bt_site's recursion without a rescale of its own -- q takes beta's)
 
 // SEG = false: one unit per sequence walks every block.  SEG = true: blockIdx.y picks a unit of the segment layout, seeded from
 // the beta scan's value at its right edge (see decode_kernel: the units, their bins and their seeds are the same).

@@ -36,10 +36,58 @@ namespace phk {
     hipError_t launch_tract_##tag(int T, int nrm, const KArgs& a, const QArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_local_##tag(int T, int nrm, const KArgs& a, const RArgs& d, int units, int nt, hipStream_t st); \
     hipError_t launch_pairs_##tag(int T, int nrm, const KArgs& a, const PArgs& d, int units, int nt, hipStream_t st); \
-    hipError_t launch_moments_##tag(int T, int nrm, const KArgs& a, const MArgs& d, int units, int nt, hipStream_t st);
+    hipError_t launch_moments_##tag(int T, int nrm, const KArgs& a, const MArgs& d, int units, int nt, hipStream_t st); \
+    hipError_t launch_interval_##tag(int T, int nrm, const KArgs& a, const IArgs& d, int units, int nt, hipStream_t st);
 PHK_DECL(f32_4) PHK_DECL(f32_8) PHK_DECL(f32_16) PHK_DECL(f32_32) PHK_DECL(f32_64)
 PHK_DECL(f64_4) PHK_DECL(f64_8) PHK_DECL(f64_16) PHK_DECL(f64_32) PHK_DECL(f64_64)
 #undef PHK_DECL
+
+// What phk_interval_tracts runs once per call before its first sweep: one wave per chunk position of the call checks the
+// position's list -- sorted, disjoint, start < end, inside [0, len - W], no interval longer than max_len -- and writes
+//   bad[s]  : 1 where the list fails (FLAG_BAD_INDEX is raised and every logp of the list is NaN: the sweep skips the list),
+//   left[y] : the leftmost first site of any good interval whose last site lies in unit y of the sweep (atomicMin; the host
+//             fills it with a huge value first).  Units are those of the segment layout for T (G = blocks per segment; G = 0: the
+//             serial plan's single unit).  Lists are sorted, so only the first interval of a list in a unit can hold the minimum.
+__global__ __launch_bounds__(64) void interval_check_kernel(const int64_t* inds, int64_t N, const int64_t* lens, int64_t Ltot, int64_t W,
+                                                           int64_t max_len, const int64_t* iv_off, const int64_t* iv_start,
+                                                           const int64_t* iv_end, int64_t S_call, int64_t B_call, int T, int G,
+                                                           double* logp, unsigned long long* left, int32_t* bad, int* risk) {
+    const int64_t s = blockIdx.x;
+    const int lane = threadIdx.x;
+    const int64_t n_iv = iv_off[S_call], lo = iv_off[s], hi = iv_off[s + 1];
+    const bool sane = lo >= 0 && hi >= lo && hi <= n_iv;  // (a list outside the arrays cannot even be marked)
+    int64_t row = inds[s];
+    if (row < 0 || row >= N) row = 0;  // (the sweep raises the flag for it)
+    int64_t len = lens != nullptr ? lens[row] : Ltot;
+    len = len > Ltot ? Ltot : len;
+    int wrong = sane ? 0 : 1;
+    if (sane) {
+        for (int64_t j = lo + lane; j < hi; j += 64) {
+            const int64_t st = iv_start[j], en = iv_end[j], prev = j > lo ? iv_end[j - 1] : 0;
+            if (st < prev || st >= en || en > len - W || en - st > max_len) wrong = 1;
+        }
+    }
+    wrong = __syncthreads_or(wrong);
+    if (lane == 0) {
+        bad[s] = wrong;
+        if (wrong && risk != nullptr) atomicOr(risk, FLAG_BAD_INDEX);
+    }
+    if (!sane) return;
+    const int segW = (G > 0 && W > 0) ? (int)((W - 1) / T) / G : 0;
+    for (int64_t j = lo + lane; j < hi; j += 64) {
+        if (wrong) {
+            for (int64_t b = 0; b < B_call; ++b) logp[b * n_iv + j] = __builtin_nan("");
+            continue;
+        }
+        const auto unit_of = [&](int64_t en) {
+            if (G <= 0) return 0;
+            const int seg = (int)(((W + en - 1) / T) / G);
+            return seg > segW ? seg - segW : 0;
+        };
+        const int y = unit_of(iv_end[j]);
+        if (j == lo || unit_of(iv_end[j - 1]) != y) atomicMin(&left[y], (unsigned long long)(W + iv_start[j]));
+    }
+}
 
 }  // namespace phk
 
@@ -150,7 +198,7 @@ struct phk_handle {
     int K = 0, device = 0, dbl = 0;
     int64_t N = 0, L = 0, Lw = 0;
     uint32_t* packed = nullptr;
-    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops, pairs, tdiff;
+    DevBuf ckpt, aux, gacc, eblk, eseg, bseg, fseg, bpi, part, tune_ll, tune_grad, risk, ops, pairs, tdiff, ivws;
     int64_t ws_limit = 0;
     int force_R = 0, force_T = 0, nrm = DEFAULT_NRM;
     int mode = -1;     // -1 auto, 0 serial, 1 segmented
@@ -1093,7 +1141,7 @@ int phk_destroy(phk_handle* h) {
     if (h->ev_join) (void)hipEventDestroy(h->ev_join);
     if (h->ev_fwd) (void)hipEventDestroy(h->ev_fwd);
     if (h->side) (void)hipStreamDestroy(h->side);
-    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops, &h->pairs, &h->tdiff})
+    for (DevBuf* b : {&h->ckpt, &h->aux, &h->gacc, &h->eblk, &h->eseg, &h->bseg, &h->fseg, &h->bpi, &h->part, &h->tune_ll, &h->tune_grad, &h->risk, &h->ops, &h->pairs, &h->tdiff, &h->ivws})
         b->release();
     if (h->packed) (void)hipFree(h->packed);
     delete h;
@@ -1219,11 +1267,12 @@ int phk_underflow_risk(phk_handle* h, int* flag) {
                                             "loo_kernel (serial sweep)", "loo_kernel (segment sweep)", "tract_kernel (serial sweep)",
                                             "tract_kernel (segment sweep)", "local_kernel (serial sweep)", "local_kernel (segment sweep)",
                                             "pairs_kernel (serial sweep)", "pairs_kernel (segment sweep)", "moments_kernel (serial sweep)",
-                                            "moments_kernel (segment sweep)", "sample_tracts_kernel"};
+                                            "moments_kernel (segment sweep)", "sample_tracts_kernel", "interval_kernel (serial sweep)",
+                                            "interval_kernel (segment sweep)"};
         return fail(PHK_EOVERRUN, "%s ran out of its loop budget at sequence %d, block/word %d (L=%lld): the call's results are invalid",
-                    names[rec[1] >= 1 && rec[1] <= 22 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
+                    names[rec[1] >= 1 && rec[1] <= 24 ? rec[1] : 0], rec[2], rec[3], (long long)h->L);
     }
-    if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld)", (long long)h->N);
+    if (word & phk::FLAG_BAD_INDEX) return fail(PHK_EINVAL, "a chunk index passed to phk_loglik was outside [0, N=%lld) (a sweep: or a row length or an interval list out of range)", (long long)h->N);
     return PHK_OK;
 }
 
@@ -1835,6 +1884,56 @@ int phk_bin_moments(phk_handle* h, const void* params, int64_t pstride_b, int64_
         return PHK_PICK(moments, h)(T, nrm, a, ma, units, 256, st);
     };
     return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, bin, Sweep("bin-moment", validate, 0, no_workspace, launch));
+}
+
+int phk_interval_tracts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,
+                        const int64_t* inds, int64_t B, int64_t S, int64_t W, int64_t max_len, const int64_t* lens,
+                        const int64_t* iv_off, const int64_t* iv_start, const int64_t* iv_end, const uint64_t* masks, int64_t mstride_b,
+                        double* ll, double* logp, void* stream) {
+    if (!h) return fail(PHK_EINVAL, "handle is NULL");
+    // (its own checks come before run_sweep's: max_len goes there in bin's place)
+    if (!iv_off || !iv_start || !iv_end) return fail(PHK_EINVAL, "the interval lists iv_off, iv_start and iv_end must be non-NULL device pointers");
+    if (!masks || !logp) return fail(PHK_EINVAL, "masks and logp must be non-NULL device pointers (one element is enough for an empty call)");
+    if (max_len < 1) return fail(PHK_EINVAL, "max_len=%lld must be >= 1 (an upper bound on end - start)", (long long)max_len);
+    if (mstride_b < 0) return fail(PHK_EINVAL, "mstride_b must be >= 0");
+    const auto validate = [] { return (int)PHK_OK; };
+    // the check's workspace: a leftmost site per unit, a flag per chunk position
+    int ws_units = 1;
+    const auto prepare = [&](int units, int64_t) {
+        ws_units = std::max(units, 1);
+        return h->ivws.ensure((size_t)ws_units * sizeof(unsigned long long) + (size_t)S * sizeof(int32_t));
+    };
+    const int64_t span = std::min<int64_t>(max_len, std::max<int64_t>(h->L, 1));  // what a unit may walk past its left edge
+    const auto launch = [&](int T, int nrm, const phk::KArgs& a, int64_t b0, int64_t s0, int units, hipStream_t st) {
+        unsigned long long* left = (unsigned long long*)h->ivws.p;
+        int32_t* bad = (int32_t*)(left + ws_units);
+        if (b0 == 0 && s0 == 0) {  // once per call, on the call's stream ahead of the first sweep
+            hipError_t e = hipMemsetAsync(left, 0x7f, (size_t)ws_units * sizeof(unsigned long long), st);
+            if (e != hipSuccess) return e;
+            hipLaunchKernelGGL(phk::interval_check_kernel, dim3((unsigned)S), dim3(64), 0, st, inds, h->N, lens, h->L, W, span, iv_off, iv_start,
+                               iv_end, S, B, T, units > 0 ? seg_blocks(T) : 0, logp, left, bad, (int*)h->risk.p);
+            e = hipGetLastError();
+            if (e != hipSuccess) return e;
+        }
+        phk::IArgs ia;
+        ia.lens = lens;
+        ia.iv_off = iv_off;
+        ia.iv_start = iv_start;
+        ia.iv_end = iv_end;
+        ia.masks = masks;
+        ia.mstride_b = mstride_b;
+        ia.b0 = b0;
+        ia.s0 = s0;
+        ia.S_call = S;
+        ia.logp = logp;
+        ia.left = left;
+        ia.bad = bad;
+        ia.search_iters = 1;
+        for (int64_t n = std::max<int64_t>(h->L - W, 1); n > 1; n >>= 1) ++ia.search_iters;
+        return PHK_PICK(interval, h)(T, nrm, a, ia, units, 256, st);
+    };
+    return run_sweep(h, {params, pstride_b, pstride_s, prefold, inds, B, S, W, ll, stream}, (int)std::min<int64_t>(span, INT32_MAX),
+                     Sweep("interval-tract", validate, 0, prepare, launch));
 }
 
 int phk_pair_counts(phk_handle* h, const void* params, int64_t pstride_b, int64_t pstride_s, const float* prefold,

@@ -105,6 +105,25 @@ struct RArgs {
     void* logratio;        // [B, S, nbin] real: log P(o | bin under the alternative) - log P(o)
 };
 
+// interval tracts (launch_interval.hip; interval_check_kernel in phk_api.hip).  The lists are the CALL's, in CSR form over its
+// chunk positions: chunk position s owns the intervals iv_off[s] .. iv_off[s + 1] - 1, sorted, disjoint, half-open, in reported
+// sites (position p is site W + p); n_iv = iv_off[S_call].
+struct IArgs {
+    const int64_t* lens;      // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all
+    const int64_t* iv_off;    // [S_call + 1]
+    const int64_t* iv_start;  // [n_iv]
+    const int64_t* iv_end;    // [n_iv]: 0 <= start < end <= len - W
+    const uint64_t* masks;    // [B, n_iv] (mstride_b = n_iv) or [n_iv] (0) of the call: bit k set = state k is inside the interval's set
+    int64_t mstride_b;
+    int64_t b0, s0;           // position of the slab in the call, and ...
+    int64_t S_call;           // ... the call's S
+    double* logp;             // [B, n_iv] of the call: log P(every site of the interval has its state in the set | o)
+    // workspace written by interval_check_kernel before the first slab's sweep
+    const unsigned long long* left;  // [max(units, 1)]: the leftmost site any sequence of the call needs from the unit (none: huge)
+    const int32_t* bad;       // [S_call]: 1 = the chunk position's list failed the check: nothing of it is swept (its logp are NaN)
+    int32_t search_iters;     // iterations of the cursor's binary search: bit length of Ltot - W, an upper bound on a list's length
+};
+
 // pair counts (launch_pairs.hip)
 struct PArgs {
     const int64_t* lens;  // [N] own length of every data row (W < len <= Ltot), or null: Ltot for all

@@ -36,6 +36,40 @@ constexpr int sweep_hold() { return sizeof(real) == 8 && T == 16 ? 4 : T; }
 template <typename real>
 constexpr int sweep_waves_per_simd(int held) { return held * SWEEP_SPL * (int)sizeof(real) <= 256 ? 2 : 1; }
 
+// q <- A (em .* q): Lane::bt_site's recursion without a rescale of its own (the tract sweep's q takes beta's, the interval
+// sweep renormalises q itself)
+template <typename L>
+__device__ __forceinline__ void tract_step(const L& lane, typename L::V (&q)[L::NP], const typename L::V (&em)[L::NP]) {
+    using V = typename L::V;
+    constexpr int NP = L::NP;
+    V w[NP], svw[NP], pbw[NP], cb;
+#pragma unroll
+    for (int h = 0; h < NP; ++h) w[h] = q[h] * em[h];
+    lane.scans_adj(w, svw, pbw, cb);
+#pragma unroll
+    for (int h = 0; h < NP; ++h) q[h] = lane.beta_prev(h, w, svw, pbw, cb);
+}
+
+__device__ __forceinline__ float log_(float x) { return logf(x); }
+__device__ __forceinline__ double log_(double x) { return log(x); }
+__device__ __forceinline__ float frexp_(float x, int* e) { return frexpf(x, e); }
+__device__ __forceinline__ double frexp_(double x, int* e) { return frexp(x, e); }
+
+// log(r 2^qe) for r >= 0: the exponent is folded into the ratio while the product is a normal number (exact: r = 1, qe = 0
+// gives 0), and added in the log domain where it is not
+template <typename real>
+__device__ __forceinline__ real local_log(real r, int qe) {
+    constexpr int LIM = sizeof(real) == 4 ? 120 : 1000;
+    int er;
+    const real m = frexp_(r, &er);  // r = m 2^er, m in [0.5, 1) (0 for r = 0)
+    const int E = er + qe;
+    if (E > -LIM && E < LIM) return log_(ldexp_(m, E));
+    // E ln 2 + log m with ln 2 in two parts of the kernel's type (the first exact in a product with |E| < 2^11)
+    constexpr real LN2_HI = sizeof(real) == 4 ? real(0x1.62ep-1) : real(0x1.62e42fefa38p-1);
+    constexpr real LN2_LO = real(0.6931471805599453094 - (double)LN2_HI);
+    return fma_(real(E), LN2_HI, fma_(real(E), LN2_LO, log_(m)));
+}
+
 // Host launchers of a sweep whose kernel is <stem>_kernel<real, K, R, T, NRM, SEG>(KArgs, DA).
 // PHK_SWEEP_TN: <stem>_tn<T, NRM>(a, d, units, nt, st), one launch; units <= 0: one serial sweep per sequence, else the
 // segment layout of the segmented plan (KArgs::seg_blocks, bseg).  TABLES: emission tables per thread in LDS (one per model).

@@ -184,6 +184,19 @@ def predictive_check(dms, data, window_size: int = 100, bin: int = 1, device=Non
     return [track[r : r + n, : (length + bin - 1) // bin] for r, n, length in spans]
 
 
+def _range_sets(dms, t_min, t_max) -> np.ndarray:
+    """bool [len(dms), M]: per model the states whose whole interval [eta.t[k], eta.t[k + 1]) (the last one open) lies inside
+    [t_min, t_max)"""
+    assert float(t_min) < float(t_max), "the TMRCA range [t_min, t_max) is empty"
+    M = dms[0].M
+    w = np.empty((len(dms), M), dtype=bool)
+    for i, dm in enumerate(dms):
+        t = np.asarray(torch.as_tensor(dm.eta.t, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(M)
+        lo, hi = t, np.append(t[1:], np.inf)
+        w[i] = (lo >= float(t_min)) & (hi <= float(t_max))
+    return w
+
+
 def tract_posterior(dms, data, t_max, t_min: float = 0.0, window_size: int = 100, bin: int = 1, weights=None, device=None,
                     double_precision: bool = False):
     """Posterior probability that the TMRCA of EVERY window of a bin of ``bin`` windows lies in [t_min, t_max), for every row of
@@ -211,12 +224,7 @@ def tract_posterior(dms, data, t_max, t_min: float = 0.0, window_size: int = 100
     M = dms[0].M
     assert all(dm.M == M for dm in dms), "all models must have the same number of states"
     if weights is None:
-        assert float(t_min) < float(t_max), "the TMRCA range [t_min, t_max) is empty"
-        w = np.empty((len(dms), M))
-        for i, dm in enumerate(dms):
-            t = np.asarray(torch.as_tensor(dm.eta.t, dtype=torch.float64).cpu().numpy(), dtype=np.float64).reshape(M)
-            lo, hi = t, np.append(t[1:], np.inf)
-            w[i] = (lo >= float(t_min)) & (hi <= float(t_max))
+        w = _range_sets(dms, t_min, t_max).astype(np.float64)
     else:
         w = np.asarray(weights.cpu() if isinstance(weights, torch.Tensor) else weights, dtype=np.float64)
         assert w.shape in ((M,), (len(dms), M)), f"weights: [{M}] or [{len(dms)}, {M}]"
@@ -563,6 +571,94 @@ def tmrca_segments(path, values=None):
         return row, start, end, state
     v = torch.as_tensor(values, dtype=torch.float64, device=p.device)
     return row, start, end, state, v[state]
+
+
+class SegmentSupport(NamedTuple):
+    """What ``segment_support`` returns (float64 device tensors; lists with one tensor per contig for a list of contigs)."""
+
+    logp: torch.Tensor  # [n]: log posterior probability of the segment's event under the equal-weight mixture of the models
+    per_model: torch.Tensor  # [B, n]: the same under each model
+
+
+def _near_sets(states, slack: int, M: int) -> np.ndarray:
+    """bool [n, M]: per segment the states within ``slack`` of the segment's own"""
+    st = np.asarray(states.cpu() if isinstance(states, torch.Tensor) else states).astype(np.int64).reshape(-1)
+    assert ((st >= 0) & (st < M)).all(), f"states outside [0, {M})"
+    assert int(slack) >= 0, "slack must be >= 0"
+    return np.abs(np.arange(M)[None, :] - st[:, None]) <= int(slack)
+
+
+def segment_support(dms, data, segments, *, states=None, slack: int = 1, t_max=None, t_min: float = 0.0, window_size: int = 100,
+                    device=None, double_precision: bool = False) -> SegmentSupport:
+    """How sure the data are of called segments: for every segment (row, start, end) the log posterior probability that the TMRCA
+    state of EVERY window of the segment lies in the segment's set -- the question after ``viterbi_tmrca`` + ``tmrca_segments``,
+    which ``tract_posterior`` answers on a fixed grid of bins and one set only.  Exact (``PSMCKernel.interval_tracts``), and a log:
+    a segment of thousands of windows has a probability far below the float range.
+
+    dms: one ``DemographicModel`` or the list ``fit()`` returns, evaluated per window as in ``posterior_tmrca``.
+    data: int8 [N, L] het matrix of whole-contig rows, or a list of ``RawContig`` (or of int8 matrices) of different lengths (padded
+        with missing windows; each row's own length bounds its segments).
+    segments: what ``tmrca_segments`` returns -- (row, start, end, state, ...) with windows ``start .. end - 1`` of row ``row`` -- in
+        any order, the segments of one row disjoint; for a list of contigs a list of such tables, rows counted per contig.
+    states / slack: the set of segment j is the states within ``slack`` of ``states[j]`` (default: the table's fourth tensor, the
+        segment's own state), the same for every model.
+    t_max / t_min: instead, the set is per model the states whose whole interval lies in [t_min, t_max), exactly as
+        ``tract_posterior`` decides it, the same for every segment.
+    Returns ``SegmentSupport(logp, per_model)``: ``per_model`` float64 [B, n] and ``logp`` = logsumexp over the models - log B,
+    the log posterior probability under the equal-weight mixture of the models (a probability given the data is linear in the
+    mixture's components, see ``tract_posterior``).  For a list of contigs: lists with one tensor per contig.
+    """
+    if isinstance(dms, DemographicModel):
+        dms = [dms]
+    dms = list(dms)
+    assert len(dms) > 0, "no model to decode under"
+    M = dms[0].M
+    assert all(dm.M == M for dm in dms), "all models must have the same number of states"
+    if isinstance(data, (list, tuple)):
+        for c in data:
+            if isinstance(c, RawContig):
+                c.get_data(window_size)  # (raises if the contig was built with another window size)
+    rows, spans = _rows(data)
+    lens = None
+    host = lambda x: np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x).astype(np.int64).reshape(-1)  # noqa: E731
+    if spans is None:
+        tables = [segments]
+        first_rows, n_rows = [0], [rows.shape[0]]
+    else:
+        tables = list(segments)
+        assert len(tables) == len(spans), "segments: one table per contig"
+        lens = np.concatenate([np.full(n, length, dtype=np.int64) for _, n, length in spans])
+        first_rows, n_rows = [r for r, _, _ in spans], [n for _, n, _ in spans]
+    counts = [host(t[0]).shape[0] for t in tables]
+    for t, nr in zip(tables, n_rows):
+        r = host(t[0])
+        if r.size and (r.min() < 0 or r.max() >= nr):
+            raise ValueError(f"segments: a row outside [0, {nr}) of its contig")
+    row = np.concatenate([host(t[0]) + r0 for t, r0 in zip(tables, first_rows)])
+    start, end = (np.concatenate([host(t[i]) for t in tables]) for i in (1, 2))
+    if t_max is not None:
+        assert states is None, "give states / slack or a time range, not both"
+        masks = np.repeat(_range_sets(dms, t_min, t_max)[:, None, :], row.shape[0], axis=1)  # [B, n, M]
+    else:
+        if states is None:
+            assert all(len(t) >= 4 for t in tables), "segments without a state column: give states or t_max"
+            st = np.concatenate([host(t[3]) for t in tables])
+        else:
+            st = np.concatenate([host(x) for x in (states if spans is not None else [states])])
+        assert st.shape[0] == row.shape[0], "states: one per segment"
+        masks = _near_sets(st, slack, M)  # [n, M]
+    kern = PSMCKernel(M, rows, double_precision=double_precision, device=device)
+    per = [DemographicModel(eta=dm.eta, theta=float(dm.theta) * window_size, rho=float(dm.rho) * window_size) for dm in dms]
+    pps = [PSMCParams.from_dm(dm) for dm in per]
+    pp = PSMCParams(*(torch.stack([torch.as_tensor(getattr(p, f), dtype=torch.float64) for p in pps])[:, None]
+                      for f in PSMCParams._fields))  # [B, 1, M]: one block per model, broadcast over the rows
+    out = kern.interval_tracts(pp, torch.arange(rows.shape[0], device=kern.device), intervals=(row, start, end), masks=masks, lens=lens)
+    per_model = out.logp  # [B, n] float64
+    logp = torch.logsumexp(per_model, 0) - float(np.log(len(dms)))
+    if spans is None:
+        return SegmentSupport(logp, per_model)
+    cuts = np.concatenate([[0], np.cumsum(counts)])
+    return SegmentSupport([logp[a:b] for a, b in zip(cuts[:-1], cuts[1:])], [per_model[:, a:b] for a, b in zip(cuts[:-1], cuts[1:])])
 
 
 class PathTracts(NamedTuple):

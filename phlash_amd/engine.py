@@ -423,6 +423,36 @@ class HipEngine:
         _lib.check(rc)
         return ll, tract
 
+    def interval_tracts(self, params: torch.Tensor, inds: torch.Tensor, iv_off: torch.Tensor, iv_start: torch.Tensor,
+                        iv_end: torch.Tensor, masks: torch.Tensor, warmup: int = 0, max_len: int = 1, lens: torch.Tensor | None = None):
+        """Interval tracts (``phk_interval_tracts``): params / inds as ``run``.  ``iv_off`` int64 [S + 1], ``iv_start`` / ``iv_end``
+        int64 [n] on the device: per chunk position the sorted, disjoint, half-open intervals ``iv_off[s] .. iv_off[s + 1] - 1`` in
+        reported sites (position p is site ``warmup + p``).  ``masks``: int64 [n] or [B, n] on the device, the state set of every
+        interval as a bit pattern (bit k set = state k is inside; bit 63 is the sign bit of the int64).  ``max_len``: an upper
+        bound on end - start.  Returns (ll [B, S] float64, logp [B, n] float64): per interval and particle log P(every site of the
+        interval has its state in the set | o).  The lists are checked on the device: one that fails raises the bad-index flag
+        (``underflow_risk`` then raises) and its logp are NaN."""
+        assert 0 <= int(warmup) <= self.L and int(max_len) >= 1
+        c = self._sweep_call(params, inds, lens)
+        n = int(iv_start.shape[0])
+        for name, x, shape in (("iv_off", iv_off, (c.S + 1,)), ("iv_start", iv_start, (n,)), ("iv_end", iv_end, (n,))):
+            assert x.is_cuda and x.device == self.device and x.dtype == torch.int64 and tuple(x.shape) == shape, f"{name}: int64 {shape} on the device"
+        assert masks.is_cuda and masks.device == self.device and masks.dtype == torch.int64, "masks: int64 on the device"
+        assert tuple(masks.shape) in ((n,), (c.B, n)), f"masks: [{n}] or [{c.B}, {n}], got {tuple(masks.shape)}"
+        if c.pad_k:  # bits of the padding states (K below the compiled size) are ignored
+            masks = masks & ((1 << self.K_user) - 1)
+        iv_off, iv_start, iv_end, masks = iv_off.contiguous(), iv_start.contiguous(), iv_end.contiguous(), masks.contiguous()
+        ll = torch.empty((c.B, c.S), dtype=torch.float64, device=self.device)
+        logp = torch.empty((c.B, n), dtype=torch.float64, device=self.device)
+        dummy = torch.zeros(1, dtype=torch.int64, device=self.device)  # (an empty tensor may have no address)
+        rc = _lib.load().phk_interval_tracts(
+            *c.head, *c.grid, int(warmup), int(max_len), c.lens, iv_off.data_ptr(), (iv_start if n else dummy).data_ptr(),
+            (iv_end if n else dummy).data_ptr(), (masks if n else dummy).data_ptr(), n if masks.ndim == 2 and c.B > 1 else 0,
+            ll.data_ptr(), (logp if n and c.B else dummy).data_ptr(), c.stream,
+        )
+        _lib.check(rc)
+        return ll, logp
+
     def bin_moments(self, params: torch.Tensor, inds: torch.Tensor, values: torch.Tensor, warmup: int = 0, bin: int = 1,
                     lens: torch.Tensor | None = None):
         """Bin moments (``phk_bin_moments``): params / inds as ``run``.  ``values``: float64 [B, K] or [K] on the device, the

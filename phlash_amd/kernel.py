@@ -101,6 +101,66 @@ class Tracts(NamedTuple):
     prob: torch.Tensor  # [..., nbin]: E[prod of weights(z_t) over the bin's sites | o]
 
 
+class IntervalTracts(NamedTuple):
+    """What ``PSMCKernel.interval_tracts`` returns (float64 device tensors)."""
+
+    ll: torch.Tensor  # log P(o), float64 (what ``posterior`` returns)
+    logp: torch.Tensor  # [n] or [B, n], the caller's order: log P(every site of the interval has its state in the set | o)
+
+
+def _host_ints(x) -> np.ndarray:
+    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x)
+
+
+def pack_state_masks(masks, n: int, B: int, M: int) -> np.ndarray:
+    """State sets as 64-bit words, uint64 [n] or [B, n]: ``masks`` as integers ([n] or [B, n], bit k set = state k is inside; a
+    negative int64 is its bit pattern) or as boolean rows ([n, M] or [B, n, M]).  Bits at or above ``M`` are dropped."""
+    m = _host_ints(masks)
+    assert M <= 64, "a state set is a 64-bit mask"
+    if m.dtype == np.bool_:
+        assert m.shape in ((n, M), (B, n, M)), f"masks: bool [{n}, {M}] or [{B}, {n}, {M}], got {m.shape}"
+        w = (m.astype(np.uint64) << np.arange(M, dtype=np.uint64)).sum(-1, dtype=np.uint64)
+    else:
+        assert m.shape in ((n,), (B, n)), f"masks: integers [{n}] or [{B}, {n}], got {m.shape}"
+        if m.dtype == object:
+            w = np.array([int(v) & ((1 << 64) - 1) for v in m.reshape(-1)], dtype=np.uint64).reshape(m.shape)
+        elif np.issubdtype(m.dtype, np.signedinteger):
+            w = m.astype(np.int64).view(np.uint64)
+        else:
+            assert np.issubdtype(m.dtype, np.unsignedinteger), f"masks: integers or booleans, got {m.dtype}"
+            w = m.astype(np.uint64)
+    return w & np.uint64((1 << M) - 1)
+
+
+def pack_intervals(intervals, own: np.ndarray):
+    """``intervals`` = (row, start, end) of n half-open intervals in reported sites, any order; ``own`` [S]: the reported sites of
+    every chunk position.  -> (order [n]: the caller's indices sorted by (row, start), iv_off [S + 1], start [n], end [n] in
+    that order, max_len).  Raises ValueError, naming the caller's entry, for a row outside [0, S), an empty interval, one out of
+    range or beyond the row's own length, and for two intervals of a row that overlap."""
+    assert len(intervals) >= 3, "intervals: (row, start, end)"
+    row, start, end = (_host_ints(x).astype(np.int64).reshape(-1) for x in intervals[:3])
+    n, S = row.shape[0], int(own.shape[0])
+    assert start.shape[0] == n and end.shape[0] == n, "intervals: row, start and end of one length"
+    order = np.lexsort((start, row))
+    r, s, e = row[order], start[order], end[order]
+
+    def first(cond, what):
+        if cond.any():
+            k = int(np.argmax(cond))
+            raise ValueError(f"interval {int(order[k])} (row {int(r[k])}, start {int(s[k])}, end {int(e[k])}): {what}")
+
+    first((r < 0) | (r >= S), f"row outside [0, {S})")
+    first(s >= e, "empty: start must be below end")
+    first(s < 0, "out of range: start below 0")
+    first(e > own[r], "out of range: end beyond the row's own length")
+    if n > 1:
+        clash = np.concatenate([[False], (r[1:] == r[:-1]) & (s[1:] < e[:-1])])
+        first(clash, "overlaps the interval before it in its row")
+    off = np.zeros(S + 1, dtype=np.int64)
+    off[1:] = np.cumsum(np.bincount(r, minlength=S))
+    return order, off, s, e, int((e - s).max()) if n else 1
+
+
 class BinMoments(NamedTuple):
     """What ``PSMCKernel.bin_moments`` returns (float64 device tensors, batch dims stripped as ``loglik`` strips them)."""
 
@@ -394,6 +454,35 @@ class PSMCKernel:
             lens = self._lens_tensor(lens)
             ll, tract = _guarded(self, "tracts", pa, inds, w, warmup=self.overlap, bin=int(bin), lens=lens)
         return Tracts(self._strip(ll, added_B, added_S), self._strip(tract, added_B, added_S))
+
+    # ---- interval tracts -----------------------------------------------------------------------
+    def interval_tracts(self, pp, index, *, intervals, masks, lens=None) -> IntervalTracts:
+        """How sure the data are of a called segment: for each of n intervals with arbitrary ends and a state set of its own,
+        ``logp`` = log P(EVERY site of the interval has its state in the set | o) -- ``tracts`` without its fixed grid and its
+        single set per call, and as a log with an exponent of its own, so a tract of thousands of sites far below the float range
+        is right.  ``intervals`` = (row, start, end): integer arrays or tensors as ``phlash_amd.tmrca_segments`` returns them
+        (further entries are ignored); ``row`` is the position in ``index``, ``start`` / ``end`` count scored sites as
+        ``viterbi``'s path does (half-open).  The intervals of one row must not overlap; any order.  ``masks``: the sets, as
+        integers [n] or [B, n] (bit k set = state k is inside) or as boolean rows [n, M] or [B, n, M]; a leading B gives every
+        particle of ``pp`` its own sets.  Chunk(s) ``index`` under ``pp`` (PSMCParams or DemographicModel, batch shapes as
+        ``loglik``).  ``lens`` ([N] integers, one own length per row of the kernel's data, ``overlap < len <= L``) bounds each
+        row's intervals.  A missing site is restricted to the set like any other.  A full set gives exactly 0, an empty one -inf.
+        Raises ValueError for an empty interval, one out of range or beyond ``lens``, and for overlapping intervals.  Returns
+        ``IntervalTracts(ll, logp)``, float64 device tensors, ``logp`` [n] or [B, n] in the caller's order; no gradient."""
+        with torch.no_grad():
+            pa, inds, added_B, added_S = self._model_inputs(pp, index)
+            B, S = pa.shape[0], inds.shape[0]
+            lens = self._lens_tensor(lens)
+            own = (lens[inds].cpu().numpy() if lens is not None else np.full(S, self.L, dtype=np.int64)) - self.overlap
+            order, off, start, end, max_len = pack_intervals(intervals, own)
+            n = order.shape[0]
+            words = pack_state_masks(masks, n, B, self.M)[..., order]
+            dev = lambda a: torch.as_tensor(np.ascontiguousarray(a), dtype=torch.int64, device=self.device)  # noqa: E731
+            ll, sorted_logp = _guarded(self, "interval_tracts", pa, inds, dev(off), dev(start), dev(end), dev(words.view(np.int64)),
+                                       warmup=self.overlap, max_len=max_len, lens=lens)
+            logp = torch.empty_like(sorted_logp)
+            logp[:, torch.as_tensor(order, device=sorted_logp.device)] = sorted_logp
+        return IntervalTracts(self._strip(ll, added_B, added_S), logp[0] if added_B else logp)
 
     # ---- bin moments ----------------------------------------------------------------------------
     def bin_moments(self, pp, index, *, values, bin: int = 1, lens=None) -> BinMoments:
